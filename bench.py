@@ -16,7 +16,12 @@ not the driver's line):
   c5  chaos game k=7, 200 M x 250 over 8 GPUs = 25 M per GPU
 
   python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4|c5]
+  python bench.py ... --full                  (+ the CPU baseline and the end-to-end CLI leg)
+  python bench.py ... --dump-outputs DIR      (the last timed step's results as DIR/<name>.npy)
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full`
+adds the legs that take runs of their own: `cpu_baseline` and, for C2, `e2e`.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N rank
 processes itself (fresh interpreters, one per GPU, before this process touches
@@ -27,8 +32,21 @@ RCCL all-reduce, whose rank count is reported as config.rccl_ranks.
 `--launch-dry-run` exercises the launcher and the read sharding on CPU (no GPU).
 
 Prints ONE JSON line (rank 0) with `roofline` (the hot kernel, HIP events on
-the engine's own stream) and `cpu_baseline` (oracle/liboracle.so, C+OpenMP,
-timed on this host's cores on a bounded sample, rank 0 at N=1 only).
+the engine's own stream: the timed steps themselves, no run of its own) and,
+with `--full`, `cpu_baseline` (oracle/liboracle.so, C+OpenMP, timed on this
+host's cores on a bounded sample, rank 0 at N=1 only) and `e2e` (C2 only).
+
+`--dump-outputs DIR` writes what the last timed step left with its caller
+(rank 0's shard; the counters / tables after the all-reduce when N > 1):
+  mask.npy      f32  the per-read (pair) pass mask          (engine configs)
+  trim.npy      f64  the per-read u32 trim words            (edit configs)
+  counters.npy  f64  the u64 counters                       (engine configs)
+  table_seq.npy, table_qual.npy, word_count.npy  f64        (c5, c5_valid)
+  kmers_by_pos.npy  f64  [1024, L-4]                        (c2_kmers)
+An array above DUMP_MAX_ELEMS elements is written as a fixed sample of that
+many elements (indices drawn once from DUMP_SEED, the same every run).  The
+inputs come from the counter-based generator, so two runs with the same
+arguments see the same reads and two builds can be compared file by file.
 """
 import argparse
 import ctypes as C
@@ -126,8 +144,13 @@ def parse():
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--reads", type=int, default=None, help="reads (pairs) per GPU")
     ap.add_argument("--batch-reads", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end CLI leg (C2)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the CPU "
+                         "baseline (one GPU) and the end-to-end CLI leg (C2)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end CLI leg (C2)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-reads", type=int, default=None,
                     help="reads of the CPU baseline's sample (default 2 M; 400 k for CGR)")
@@ -147,6 +170,8 @@ def parse():
         ap.error("--gpus must be >= 1")
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.config == "dropin":
+        ap.error("--dump-outputs: --config dropin times a C harness that returns no arrays")
     cfg = CONFIGS[a.config]
     a.reads = a.reads or cfg["reads"]
     a.batch_reads = a.batch_reads or cfg["batch"]
@@ -733,6 +758,29 @@ def result_line(args, cfg, world, el, steps_reads, roofline, rccl_ranks, dtype, 
 
 RANK_KEYS = ("rank", "device", "pci", "uuid", "el_s", "avg_launch_us")
 
+# ---- --dump-outputs: the last timed step's results as .npy ------------------
+DUMP_MAX_ELEMS = 4_000_000   # per array: mask (f32) 16 MB + trim (f64) 32 MB stay under 64 MB in all
+DUMP_SEED = 20240229
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each array of `arrays` (name -> integer numpy array) as
+    out_dir/<name>.npy: float32 where every value is exact in it (the 0/1
+    mask), float64 otherwise (u32 / u64 counts below 2^53).  An array above
+    DUMP_MAX_ELEMS elements is sampled at DUMP_MAX_ELEMS flat indices drawn
+    from DUMP_SEED and the array's size alone, sorted: the same elements in
+    every run with the same arguments.  At most 4 M x (4 + 8) B + the small
+    arrays = 48 MB + < 2 MB."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        flat = np.ascontiguousarray(a).reshape(-1)
+        shape = a.shape
+        if flat.size > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.size, DUMP_MAX_ELEMS))
+            flat, shape = flat[pick], (DUMP_MAX_ELEMS,)
+        dt = np.float32 if a.dtype == np.uint8 else np.float64
+        np.save(os.path.join(out_dir, name + ".npy"), flat.astype(dt).reshape(shape))
+
 
 def dry_run_rank(args, world, rank):
     """--launch-dry-run: the rank plumbing on CPU.  Each rank derives its read
@@ -782,7 +830,7 @@ def dry_run_rank(args, world, rank):
                 sys.exit(3)
         out = result_line(args, cfg, world, None, 0, None, None, "u8", extra)
         out["dry_run"] = True
-        if world == 1 and not args.no_cpu_baseline:   # the CPU leg needs no device
+        if world == 1 and args.full and not args.no_cpu_baseline:   # the CPU leg needs no device
             out["cpu_baseline"] = cpu_baseline(args, params_for(args.config, args.read_length))
         print(json.dumps(out), flush=True)
     if world > 1:
@@ -831,7 +879,8 @@ def main():
     mates = 2 if params.paired else 1
     batches = make_batches(args, rank, dev, mates)
     d_mask = torch.empty(args.reads, dtype=torch.uint8, device=dev)
-    d_trim = torch.empty(args.reads * mates, dtype=torch.int32, device=dev)
+    # (zeroed: a trim word the kernels leave unwritten reads the same in every run's dump)
+    d_trim = torch.zeros(args.reads * mates, dtype=torch.int32, device=dev)
     offs = np.cumsum([0] + [b[0] for b in batches])
 
     statuses = []
@@ -946,15 +995,24 @@ def main():
         el = max(g["el_s"] for g in ranks)
 
     # sanity: every read accounted for (after the all-reduce: every rank's reads)
+    # (`outputs`: what the last timed step left with its caller, for --dump-outputs)
     if kmers:
-        assert int(km.by_pos().sum()) > 0 or os.environ.get("HPGQ_BENCH_NOCHECK")   # (timing probes)
+        by_pos = km.by_pos()
+        assert int(by_pos.sum()) > 0 or os.environ.get("HPGQ_BENCH_NOCHECK")   # (timing probes)
+        outputs = {"kmers_by_pos": by_pos}
     elif cgr:
-        _ts, _tq, wc = eng.tables()
+        ts, tq, wc = eng.tables()
         assert wc > 0 or os.environ.get("HPGQ_BENCH_NOCHECK")   # (timing-probe builds add nothing)
+        outputs = {"table_seq": ts, "table_qual": tq, "word_count": np.array([wc], np.uint32)}
     else:
         ctr = eng.counters()
         expect = args.reads * world
         assert int(ctr[H.S_NUM_INPUT]) == expect, (int(ctr[H.S_NUM_INPUT]), expect)
+        outputs = {"counters": ctr}
+        if rank == 0 and args.dump_outputs:   # the device arrays come to the host only when asked for
+            outputs["mask"] = d_mask.cpu().numpy()
+            if params.edit_on:
+                outputs["trim"] = d_trim.cpu().numpy().view(np.uint32)
 
     total = args.reads * world * args.steps
     avg_launch_s = timed_ms / (args.steps * nb) / 1e3
@@ -990,9 +1048,11 @@ def main():
     if args.share_device:
         extra["shared_device"] = f"{world} ranks on {ndev} device(s): functional run, not a scaling number"
     out = result_line(args, cfg, world, el, total, roofline, rccl_ranks, "f64" if cgr else "u8", extra)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, params)
-    if rank == 0 and world == 1 and args.config == "c2" and not args.no_e2e:
+    if rank == 0 and world == 1 and args.config == "c2" and args.full and not args.no_e2e:
         eng.close()   # (the CLI runs in its own process)
         eng = None
         out["e2e"] = e2e_leg(args, local_dev)

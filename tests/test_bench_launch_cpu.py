@@ -68,11 +68,44 @@ def test_one_gpu_line_shape_unchanged():
     assert "ranks" not in line["config"]
 
 
+def test_plain_run_leaves_the_cpu_baseline_to_full():
+    """Without --full the line carries no leg that takes a run of its own."""
+    r = _bench("--gpus", "1", "--launch-dry-run", "--reads", "5000")
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert set(line) - {"dry_run"} == LINE_KEYS
+    assert "cpu_baseline" not in line and "e2e" not in line
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs' writer: float32 / float64 .npy, large arrays as the same
+    DUMP_MAX_ELEMS elements every time, small ones whole and exact."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n = bench.DUMP_MAX_ELEMS + 12345
+    mask = (np.arange(n) % 3 == 0).astype(np.uint8)
+    ctr = np.array([0, 1, 2**40 + 1], np.uint64)
+    tab = np.arange(16, dtype=np.uint32).reshape(4, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"mask": mask, "counters": ctr, "table_seq": tab})
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(a) == ["counters.npy", "mask.npy", "table_seq.npy"]
+    for f, v in a.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f))
+    assert a["mask.npy"].dtype == np.float32 and a["mask.npy"].shape == (bench.DUMP_MAX_ELEMS,)
+    pick = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, bench.DUMP_MAX_ELEMS))
+    assert np.array_equal(a["mask.npy"], mask[pick].astype(np.float32))
+    assert a["counters.npy"].dtype == np.float64 and [int(x) for x in a["counters.npy"]] == [0, 1, 2**40 + 1]
+    assert a["table_seq.npy"].shape == (4, 4) and np.array_equal(a["table_seq.npy"], tab)
+    assert sum(v.nbytes for v in a.values()) <= 64 * 2**20
+
+
 def test_one_gpu_line_cpu_baseline_keys():
     """The one-GPU line's CPU leg (no device needed): the oracle on this GPU's
     CPU share, on one thread, and on every visible core (VERDICT r5 item 5:
     SURVEY §8d's threads = nproc), with the C1 and reference-architecture legs."""
-    r = _bench("--gpus", "1", "--launch-dry-run", "--reads", "5000", "--cpu-seconds", "0.3",
+    r = _bench("--gpus", "1", "--launch-dry-run", "--full", "--reads", "5000", "--cpu-seconds", "0.3",
                "--cpu-reads", "20000")
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

@@ -12,7 +12,7 @@ export TMPDIR=/tmp
 P=${P:-gpurun_out/prof}
 mkdir -p $P
 if [ -z "$SKIP_TRACE" ]; then
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-e2e > $P/bench.json 2> $P/trace.err || exit 3
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --no-e2e > $P/bench.json 2> $P/trace.err || exit 3
 fi
 for spec in ${SPECS:-c2:c2:10000000:150 c3:pe:10000000:150 c4:edit:12500000:150 c4_noor:edit_noor:12500000:150 c4_pe:pe_edit:10000000:150 c5:cgr:5000000:250 c5_valid:cgrv:5000000:250 c2_lr:lr:10000000:150 c2_250:c2:5000000:250 c2_kmers:c2:10000000:150:--kmers}; do
   IFS=: read cfg mode n L extra <<< "$spec"
