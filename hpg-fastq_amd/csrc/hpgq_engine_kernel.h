@@ -1000,17 +1000,23 @@ __global__ void __launch_bounds__(kWG) engine_kernel(EngineArgs A) {
     };
 
     // group g of this unit sits in slot g & 1; the group after the last one
-    // is the next unit's group 0 (full units have an even group count, so it
-    // lands in slot 0, where the next unit expects it)
+    // is the next unit's group 0, which the next unit expects in slot 0: an
+    // even group count (every full unit) puts it there a group ahead; an odd
+    // one (a follow-up unit of an odd number of deferred reads, a batch's last
+    // unit) loads it once slot 0 is free, after the unit's last group.  (It
+    // used to go to slot 1 then, and the next unit counted its first group
+    // from the stale slot 0: wrong masks and counters for a wave's second and
+    // later follow-up units.)
     const int ngroups = (nr + kU - 1) / kU;
     for (int g = 0; g < ngroups; g += 2) {
       if (g + 1 < ngroups) load_group(os, oq, al, ln, nr, g + 1, 1);
-      else load_group(osn, oqn, aln, lnn, nxt.nr, 0, 1);
       process_group(g, 0);
       if (g + 1 < ngroups) {
         if (g + 2 < ngroups) load_group(os, oq, al, ln, nr, g + 2, 0);
         else load_group(osn, oqn, aln, lnn, nxt.nr, 0, 0);
         process_group(g + 1, 1);
+      } else {
+        load_group(osn, oqn, aln, lnn, nxt.nr, 0, 0);
       }
     }
 

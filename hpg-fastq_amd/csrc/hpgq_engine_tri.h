@@ -727,24 +727,42 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
   // and its N / out-of-range variants: round 6, one box, 3 alternating rounds,
   // C2 528.6 -> 523.5 us); the others re-read lines the stream brought in
   // (trim windows, step-boundary lines) and ran 3-4 % slower with nt
-  // (C3 1107 -> 1147, C4 815 -> 840; profiles/r06_nt_ab.json)
-  constexpr int kAux = PF ? 2 : 0;
-  auto gather_at = [&](int m, int tb, uint32_t eoff, TriPending<NW> &pd) __attribute__((always_inline)) {
+  // (C3 1107 -> 1147, C4 815 -> 840; profiles/r06_nt_ab.json).
+  // Round 7: the LAST step of every group keeps the plain policy (kAuxLast,
+  // load_group).  A group's last step and the next group's first share a
+  // cache line per buffer, and the two loads lie a group of work (~2.5 us)
+  // apart: an nt line is its L2 set's first victim and was gone by then, so
+  // the line came from HBM twice (+182 MB per 10 M-read launch, 1.088x the
+  // algorithmic bytes); a plainly allocated line is still there when the next
+  // group's nt load takes it (1.026x; same box, 4 alternating rounds, C2 525.6 -> 502.3 us;
+  // DESIGN.md 4.1, profiles/r07_stream_boundary_rates.json)
+  // (the N / out-of-range variants keep nt on every step, round 6's code:
+  // VALU-bound at 0.60 of the HBM rate, they gain nothing from the smaller
+  // fetch and ran 0.26 % and 1.09 % slower with it in two 4-round sessions,
+  // profiles/r07_c2_boundary_ab.json, noor_with_plain_last_step)
+  constexpr int kAux = PF ? 2 : 0, kAuxLast = NX ? kAux : 0;
+  auto gather_at = [&](int m, int tb, uint32_t eoff, TriPending<NW> &pd, bool last = false) __attribute__((always_inline)) {
     const v4u rec = *reinterpret_cast<const v4u *>(reinterpret_cast<const uint8_t *>(tab(m, tb)) + eoff);
     pd.n = rec.z;
-    if (NW == 2) {
-      const v2u a = __builtin_amdgcn_raw_buffer_load_b64(rs[m], rec.x + lane8, 0, kAux);
-      const v2u b = __builtin_amdgcn_raw_buffer_load_b64(rq[m], rec.y + lane8, 0, kAux);
-      pd.s[0] = a.x; pd.s[1] = a.y; pd.q[0] = b.x; pd.q[1] = b.y;
-    } else {
-      const v4u a = __builtin_amdgcn_raw_buffer_load_b128(rs[m], rec.x + lane8, 0, kAux);
-      const v4u b = __builtin_amdgcn_raw_buffer_load_b128(rq[m], rec.y + lane8, 0, kAux);
+    auto words = [&](auto aux_tag) __attribute__((always_inline)) {
+      constexpr int aux = decltype(aux_tag)::value;
+      if (NW == 2) {
+        const v2u a = __builtin_amdgcn_raw_buffer_load_b64(rs[m], rec.x + lane8, 0, aux);
+        const v2u b = __builtin_amdgcn_raw_buffer_load_b64(rq[m], rec.y + lane8, 0, aux);
+        pd.s[0] = a.x; pd.s[1] = a.y; pd.q[0] = b.x; pd.q[1] = b.y;
+      } else {
+        const v4u a = __builtin_amdgcn_raw_buffer_load_b128(rs[m], rec.x + lane8, 0, aux);
+        const v4u b = __builtin_amdgcn_raw_buffer_load_b128(rq[m], rec.y + lane8, 0, aux);
 #pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        pd.s[w] = a[w & 3];
-        pd.q[w] = b[w & 3];
+        for (int w = 0; w < NW; ++w) {
+          pd.s[w] = a[w & 3];
+          pd.q[w] = b[w & 3];
+        }
       }
-    }
+    };
+    // (kernels with one policy: the condition is a constant, one set of loads)
+    if (kAuxLast != kAux && last) words(TriTag<kAuxLast>{});
+    else words(TriTag<kAux>{});
   };
   auto gather = [&](int m, int tb, int src, TriPending<NW> &pd) __attribute__((always_inline)) {
     gather_at(m, tb, 16u * (uint32_t)src, pd);
@@ -779,7 +797,8 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
   auto load_group = [&](int m, int tb, int nt, int g, int slot) __attribute__((always_inline)) {
 #pragma unroll
     for (int u = 0; u < kU; ++u) {
-      gather_at(m, tb, step_off(g * kU + u, nt), grp[slot][u]);
+      // (the group's last step plain: its trailing line waits in L2 for the next group)
+      gather_at(m, tb, step_off(g * kU + u, nt), grp[slot][u], u == kU - 1);
     }
     if (ST && slot == 0) {   // (the pair's windows, after group g's stream loads: the same lines)
       const int r = lane >> 1, h = lane & 1, idx = kSegs * kU * g + r;

@@ -6,10 +6,14 @@
 //          of a 150-byte read starting at its (unaligned, dword-rounded) offset
 //   hex    6 reads per step, 10 lanes x 16 B of a 150-byte read
 // Each lane XOR-folds what it loads (kept alive through one store per lane).
+//   units  the hex kernel's unit / group issue order and load policies (k_units;
+//          `./stream_rates units [chain ...]` runs only these)
 //   hipcc --offload-arch=gfx950 -O3 stream_rates.hip -o stream_rates && ./stream_rates
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
+#include <cstdlib>
+#include <string>
 #include <vector>
 
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
@@ -116,7 +120,124 @@ __global__ void __launch_bounds__(kWG) k_reads(const char *a, const char *b, uin
   out[blockIdx.x * kWG + threadIdx.x] = x;
 }
 
-int main() {
+// The pass-first hex kernel's issue order (tri_body, PF): a wave owns
+// contiguous 48-read units, grid-strided by unit; a unit is 4 groups of 2
+// steps, a step 6 reads x 10 lanes x 16 B at the read's dword-rounded offset
+// (lanes 60-63 run on into the next step's first read, as in the kernel),
+// both buffers.  Group g + 1 is issued, group g consumed, every load waited
+// for (s_waitcnt vmcnt(0)), then group g + 2 issued (the next unit's first
+// group at a unit's end).  Consuming a group folds its 16 dwords and runs a
+// dependent chain of `chain` (v_xor, v_add) pairs; 110 pairs give the
+// kernel's ~239 VALU per group.  The read offsets go through a
+// per-wave LDS table written a unit ahead, as the kernel's read table.
+// V: 0 every stream load plain; 1 every one nt; 2 nt plus a keep-alive touch
+// BEFORE the group's stream loads (one lane per buffer loads, plain policy,
+// the first dword of the NEXT group's first read; the other lanes pass an
+// out-of-range offset: zeros, no traffic); 3 the same touch AFTER them; 4 no
+// touch, the group's last step plain and its first nt.
+constexpr int kUR = 48, kUS = 6, kUG = 2;   // reads per unit, per step; steps per group
+template <int V>
+__global__ void __launch_bounds__(kWG, 4) k_units(const char *a, const char *b, uint32_t n, const int32_t *idx,
+                                                  int64_t nreads, uint32_t *out, int chain) {
+  __shared__ uint32_t tabs[kWG / 64][2][64];
+  const auto ra = rsrc(a, n + 64), rb = rsrc(b, n + 64);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const uint32_t lane16 = 16u * (uint32_t)(lane % 10);
+  const int seg = lane / 10;   // 6: lanes 60-63
+  constexpr uint32_t kOut = 0xC0000000u;
+  const int64_t nunits = (nreads + kUR - 1) / kUR;
+  const int64_t nw = (int64_t)gridDim.x * (kWG / 64);
+  int64_t u = (int64_t)blockIdx.x * (kWG / 64) + w;
+  // lane j: read j of unit un (entries past the data: out of range), fetched
+  // a unit ahead of the table write so that write waits for no load in flight
+  auto fetch = [&](int64_t un) {
+    const int64_t r = un * kUR + lane;
+    return (un < nunits && lane < kUR && r < nreads) ? (uint32_t)idx[r] : kOut;   // (rounded at the write: no wait here)
+  };
+  uint32_t ahead = 0;
+  auto describe = [&](int64_t un, int tb) {
+    tabs[w][tb][lane] = ahead & ~3u;
+    __builtin_amdgcn_wave_barrier();
+    ahead = fetch(un + nw);
+  };
+  v4u ps[2][kUG], pq[2][kUG];
+  uint32_t tk[2][2] = {{0u, 0u}, {0u, 0u}};
+  auto touch = [&](int tb, int g, int slot) {
+    const bool lastg = g == kUR / (kUS * kUG) - 1;
+    const uint32_t o = tabs[w][lastg ? tb ^ 1 : tb][lastg ? 0 : kUS * kUG * (g + 1)];
+    const uint32_t t = lane == 0 ? o : kOut;
+    tk[slot][0] = __builtin_amdgcn_raw_buffer_load_b32(ra, t, 0, 0);
+    tk[slot][1] = __builtin_amdgcn_raw_buffer_load_b32(rb, t, 0, 0);
+  };
+  auto load_group = [&](int tb, int g, int slot) {
+    if (V == 2) touch(tb, g, slot);
+#pragma unroll
+    for (int s = 0; s < kUG; ++s) {
+      const uint32_t o = tabs[w][tb][kUS * (g * kUG + s) + seg] + lane16;
+      if (V == 0 || (V == 4 && s == kUG - 1)) {
+        ps[slot][s] = __builtin_amdgcn_raw_buffer_load_b128(ra, o, 0, 0);
+        pq[slot][s] = __builtin_amdgcn_raw_buffer_load_b128(rb, o, 0, 0);
+      } else {
+        ps[slot][s] = __builtin_amdgcn_raw_buffer_load_b128(ra, o, 0, 2);
+        pq[slot][s] = __builtin_amdgcn_raw_buffer_load_b128(rb, o, 0, 2);
+      }
+    }
+    if (V == 3) touch(tb, g, slot);
+  };
+  uint32_t x = 0;
+  auto consume = [&](int slot) {
+#pragma unroll
+    for (int s = 0; s < kUG; ++s)
+      x ^= ps[slot][s].x ^ ps[slot][s].y ^ ps[slot][s].z ^ ps[slot][s].w ^ pq[slot][s].x ^ pq[slot][s].y ^
+           pq[slot][s].z ^ pq[slot][s].w;
+    for (int i = 0; i < chain; ++i) x = (x ^ 0x9E3779B9u) + (uint32_t)i;   // v_xor, v_add: dependent
+  };
+  int tb = 0;
+  if (u < nunits) {
+    ahead = fetch(u);
+    describe(u, tb);
+    load_group(tb, 0, 0);
+  }
+  while (u < nunits) {
+    describe(u + nw, tb ^ 1);
+    constexpr int ng = kUR / (kUS * kUG);
+#pragma unroll
+    for (int g = 0; g < ng; g += 2) {
+      load_group(tb, g + 1, 1);
+      __builtin_amdgcn_sched_barrier(0);   // (issue first, as the kernel does; hipcc would start the fold above the loads)
+      consume(0);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (V == 2 || V == 3) asm volatile("" ::"v"(tk[0][0]), "v"(tk[0][1]), "v"(tk[1][0]), "v"(tk[1][1]));
+      if (g + 2 < ng) load_group(tb, g + 2, 0);
+      else load_group(tb ^ 1, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      consume(1);
+    }
+    u += nw;
+    tb ^= 1;
+  }
+  out[blockIdx.x * kWG + threadIdx.x] = x;
+}
+
+// `stream_rates units [chain ...]`: only the unit-order kernels, one line per
+// variant and chain length (4 workgroups per CU, the engine's persistent grid)
+template <int V>
+void run_units(const char *a, const char *b, uint32_t n, const int32_t *idx, int64_t nreads, uint32_t *out, int cus,
+               int chain, hipEvent_t e0, hipEvent_t e1) {
+  const int grid = cus * 4, reps = 10;
+  k_units<V><<<grid, kWG>>>(a, b, n, idx, nreads, out, chain);
+  hipDeviceSynchronize();
+  hipEventRecord(e0);
+  for (int i = 0; i < reps; ++i) k_units<V><<<grid, kWG>>>(a, b, n, idx, nreads, out, chain);
+  hipEventRecord(e1);
+  hipEventSynchronize(e1);
+  float ms = 0;
+  hipEventElapsedTime(&ms, e0, e1);
+  std::printf("units V%d chain %3d: %.1f us/pass  %.3f TB/s\n", V, chain, ms / reps * 1e3,
+              2.0 * n * reps / (ms * 1e-3) / 1e12);
+}
+
+int main(int argc, char **argv) {
   const int64_t nreads = 10000000;
   const uint32_t n = (uint32_t)(nreads * kL);
   char *a, *b;
@@ -136,6 +257,19 @@ int main() {
   hipEvent_t e0, e1;
   hipEventCreate(&e0);
   hipEventCreate(&e1);
+  if (argc > 1 && std::string(argv[1]) == "units") {
+    std::vector<int> chains;
+    for (int i = 2; i < argc; ++i) chains.push_back(std::atoi(argv[i]));
+    if (chains.empty()) chains.push_back(110);
+    for (int c : chains) {
+      run_units<0>(a, b, n, idx, nreads, out, cus, c, e0, e1);
+      run_units<1>(a, b, n, idx, nreads, out, cus, c, e0, e1);
+      run_units<2>(a, b, n, idx, nreads, out, cus, c, e0, e1);
+      run_units<3>(a, b, n, idx, nreads, out, cus, c, e0, e1);
+      run_units<4>(a, b, n, idx, nreads, out, cus, c, e0, e1);
+    }
+    return 0;
+  }
   auto run = [&](const char *name, auto launch) {
     for (int occ : {4, 8, 16}) {
       const int grid = cus * occ;
