@@ -86,6 +86,7 @@ struct hpgq_ctx {
   uint32_t min_seq = 0;      // reports older than this (before a probe) are ignored
   int parity = 0;
   int route = HPGQ_ROUTE_AUTO;   // hpgq_debug_set_route (tests, A/B); never from the environment
+  int max_wg = 0;                // hpgq_debug_set_max_workgroups (tests): workgroups per stage, 0 = no limit
   int cus = 0;
   uint64_t *d_bits1 = nullptr, *d_bits2 = nullptr;   // deferred reads per s1 unit
   size_t bits_cap = 0;
@@ -610,10 +611,16 @@ static int ensure_bits(hpgq_ctx *c, int64_t n) {
   return HPGQ_OK;
 }
 
+// workgroups a stage may launch: its persistent grid, capped by
+// hpgq_debug_set_max_workgroups (tests: a small grid gives every wave many units)
+static int stage_grid(const hpgq_ctx *c, const Stage &s) {
+  return c->max_wg > 0 ? std::min(s.grid, c->max_wg) : s.grid;
+}
+
 static int launch_stage(hpgq_ctx *c, const Stage &s, hpgq::EngineArgs &A) {
   const int64_t units = s.follow ? A.nunits : (A.num_reads + s.block - 1) / s.block;
   const int64_t need = (units + hpgq::kWaves - 1) / hpgq::kWaves;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(need, s.grid));
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(need, stage_grid(c, s)));
   void *args[] = {&A};
   HPGQ_HIP_TRY(hipLaunchKernel(s.fn, dim3(grid), dim3(hpgq::kWG), args, s.lds, c->stream));
   return HPGQ_OK;
@@ -1248,6 +1255,33 @@ int hpgq_debug_set_route(hpgq_ctx_t *c, int route) {
   c->mode = 0;
   c->wide_calls = 0;
   c->min_seq = c->seq + 1;
+  return HPGQ_OK;
+}
+
+// the grid cap and the grids it caps, for tests that need several units per
+// wave of a stage (never read from the environment; kept by
+// hpgq_debug_set_route and hpgq_reset)
+int hpgq_debug_set_max_workgroups(hpgq_ctx_t *c, int max_wg) {
+  if (!c || max_wg < 0) return HPGQ_E_INVALID;
+  c->max_wg = max_wg;   // (host state only: launch_stage reads it at the next call)
+  return HPGQ_OK;
+}
+
+int hpgq_debug_stage_waves(const hpgq_ctx_t *c, int chain, int stage, int *waves, int *unit_reads) {
+  if (!c || !waves || !unit_reads || chain < 0 || chain > (c->adaptive ? 1 : 0)) return HPGQ_E_INVALID;
+  const Chain &ch = c->ch[chain];
+  const Stage *s = nullptr;
+  int block = ch.s1.block;   // follow-up stages iterate over the first stage's units
+  switch (stage) {
+    case 1: s = &ch.s1; break;
+    case 2: s = ch.has2 ? &ch.s2 : nullptr; break;
+    case 3: s = ch.has3 ? &ch.s3 : nullptr; break;
+    case 4: s = &c->redo; block = 64; break;   // the long-read tail's second pass (resolve)
+    default: break;
+  }
+  if (!s || !s->fn) return HPGQ_E_INVALID;
+  *waves = stage_grid(c, *s) * hpgq::kWaves;
+  *unit_reads = block;
   return HPGQ_OK;
 }
 

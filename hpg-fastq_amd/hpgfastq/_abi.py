@@ -121,6 +121,9 @@ _SIGS = [
     ("hpgq_global_counters_device", C.c_void_p, [C.c_void_p]),
     ("hpgq_comm_count", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     ("hpgq_debug_set_route", C.c_int, [C.c_void_p, C.c_int]),
+    ("hpgq_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
+    ("hpgq_debug_stage_waves", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                         C.POINTER(C.c_int)]),
     ("hpgq_cgr_open", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int]),
     ("hpgq_cgr_close", None, [C.c_void_p]),
     ("hpgq_cgr_fill_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_int]),

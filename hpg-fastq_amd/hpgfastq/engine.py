@@ -55,6 +55,20 @@ class Engine:
         'hex' / 'wide' first, 'auto_fixed' (no adaptive first stage)."""
         check(lib.hpgq_debug_set_route(self._h, ROUTES[route]), "hpgq_debug_set_route")
 
+    def set_max_workgroups(self, n):
+        """hpgq_debug_set_max_workgroups: at most n workgroups per stage (0: no
+        limit); tests only."""
+        check(lib.hpgq_debug_set_max_workgroups(self._h, int(n)), "hpgq_debug_set_max_workgroups")
+
+    def stage_waves(self, stage, chain=0):
+        """hpgq_debug_stage_waves -> (waves the stage launches at most, reads
+        per unit it iterates over); stage 1..3, or 4 for the long-read tail's
+        second pass.  HpgqError(-1) for a stage the chain does not have."""
+        w, b = C.c_int(0), C.c_int(0)
+        check(lib.hpgq_debug_stage_waves(self._h, int(chain), int(stage), C.byref(w), C.byref(b)),
+              "hpgq_debug_stage_waves")
+        return w.value, b.value
+
     def close(self):
         if self._h:
             lib.hpgq_close(self._h)

@@ -349,6 +349,23 @@ int  hpgq_comm_count(hpgq_ctx_t *ctx, int *count);
 #define HPGQ_ROUTE_FIRST_WIDE  4
 #define HPGQ_ROUTE_NO_ADAPTIVE 0x10
 int  hpgq_debug_set_route(hpgq_ctx_t *ctx, int route);
+/*
+ * Tests only: launch at most max_wg workgroups per stage (0, the default: no
+ * limit), the long-read tail's second pass included, so that a small batch
+ * gives every wave of a stage several units.  Never read from the
+ * environment; kept across hpgq_debug_set_route and hpgq_reset.
+ * HPGQ_E_INVALID for a NULL ctx or a negative value.
+ */
+int  hpgq_debug_set_max_workgroups(hpgq_ctx_t *ctx, int max_wg);
+/*
+ * The waves stage `stage` of chain `chain` launches at most (its persistent
+ * grid under the limit above, times the waves per workgroup) and the reads
+ * per unit it iterates over.  chain: 0, or 1 for the adaptive wide-first
+ * chain; stage: 1 (its own block), 2 and 3 (the follow-up stages: the first
+ * stage's block), 4 (the long-read tail's second pass: 64).  HPGQ_E_INVALID
+ * for a chain or stage the ctx does not have.
+ */
+int  hpgq_debug_stage_waves(const hpgq_ctx_t *ctx, int chain, int stage, int *waves, int *unit_reads);
 
 /* ---------------------------------------------------------------------- */
 /* chaos-game (CGR) accumulator, old/chaos_game.c:165-267                 */

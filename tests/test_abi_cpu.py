@@ -91,6 +91,11 @@ def test_synth_length_matches_indices():
 
 def test_invalid_arguments_rejected():
     assert H.lib.hpgq_counters_summary(None, 10, None) == -1
+    # the debug entry points on a NULL ctx (HPGQ_E_INVALID before any device call)
+    assert H.lib.hpgq_debug_set_route(None, 0) == -1
+    assert H.lib.hpgq_debug_set_max_workgroups(None, 2) == -1
+    w, b = C.c_int(0), C.c_int(0)
+    assert H.lib.hpgq_debug_stage_waves(None, 0, 1, C.byref(w), C.byref(b)) == -1
     p = H.params_default(lmax=H.LMAX_LIMIT + 1)
     h = C.c_void_p()
     assert H.lib.hpgq_open(C.byref(h), 0, C.byref(p)) in (-1, -5)
