@@ -1,7 +1,8 @@
 // hpgq_engine.hip — libhpgq: engine context, the kernel chain and the C-ABI.
 // The kernels live in hpgq_engine_kernel.h (catch-all, routing) and
 // hpgq_engine_tri.h (segmented), instantiated per geometry in
-// hpgq_engine_geo.hip.
+// hpgq_engine_geo.hip; their LDS layouts, which also size every launch here,
+// in hpgq_engine_lds.h.
 
 #include "hpgq_engine_kernel.h"
 #include "hpgq_engine_tri.h"
@@ -22,20 +23,19 @@ namespace {
 
 // one kernel of the chain
 struct Stage {
-  const void *fn = nullptr;
+  hpgq::KernelDesc k;
   size_t lds = 0;
   int grid = 0;
-  int block = 0;           // reads per unit (direct stages)
-  int defer_len = INT_MAX;
+  int defer_len = INT_MAX;   // longer reads go to the next stage
   bool follow = false;
-  char name[80] = {0};
 };
 
-// the kernels of one call: s1 takes the batch; s2 (wide segmented) and s3
-// (catch-all) take what the stage before deferred
+// the kernels of one call: st[0] takes the batch, each later one what the
+// stage before it deferred; the last is the catch-all unless the first is a
+// segmented kernel nothing follows (n == 1: the catch-all alone)
 struct Chain {
-  Stage s1, s2, s3;
-  bool has2 = false, has3 = false;
+  Stage st[3];
+  int n = 0;
 };
 
 // flags words behind the counters (one memset clears both): deferred-read
@@ -227,76 +227,40 @@ static const void *kernel_nch(int nch) {
 
 // the catch-all kernel: chunk count from lmax (the pipelined loads must hold
 // every read the counters can hold; longer reads take its chunk loop)
-static void catch_all(Stage &s, int nm, int lmax, bool gen, bool follow) {
+static hpgq::KernelDesc catch_all(int nm, int lmax, bool gen, bool follow) {
+  hpgq::KernelDesc k;
   int nch = (lmax + hpgq::kChunk - 1) / hpgq::kChunk;
   if (nch > 2 || follow) nch = 5;   // instantiated chunk counts: 1, 2, 5
   if (follow)   // the follow-up instance: every option, five chunks (reads <= 1260 pipelined)
-    s.fn = nm == 2 ? (const void *)hpgq::engine_kernel<2, 5, true, true>
+    k.fn = nm == 2 ? (const void *)hpgq::engine_kernel<2, 5, true, true>
                    : (const void *)hpgq::engine_kernel<1, 5, true, true>;
   else
-    s.fn = nm == 2 ? (gen ? kernel_nch<2, true>(nch) : kernel_nch<2, false>(nch))
+    k.fn = nm == 2 ? (gen ? kernel_nch<2, true>(nch) : kernel_nch<2, false>(nch))
                    : (gen ? kernel_nch<1, true>(nch) : kernel_nch<1, false>(nch));
-  s.follow = follow;
-  s.block = 64;
-  std::snprintf(s.name, sizeof(s.name), "hpgq::engine_kernel<%d, %d, %s>%s", nm, nch, gen ? "true" : "false",
+  k.block = 64;
+  k.pos = INT_MAX;
+  k.lds_bytes = nm == 2 ? hpgq::CatchAllLds<2>::bytes_for : hpgq::CatchAllLds<1>::bytes_for;
+  std::snprintf(k.name, sizeof(k.name), "hpgq::engine_kernel<%d, %d, %s>%s", nm, nch, gen ? "true" : "false",
                 follow ? " (follow-up)" : "");
+  return k;
 }
 
-static size_t seg_lds(const hpgq_params_t &p, int nm, int xm, int pos, bool follow = false, int block = 0) {
-  const size_t lp = (size_t)std::min(p.lmax, pos);   // the kernel's on-chip positions (tri_body: lp)
-  const size_t hlen = lp + 1 + HPGQ_MEANQ_BINS + HPGQ_GC_BINS;
-  const size_t mate_words = (size_t)6 * lp + ((hlen + 1) & ~(size_t)1) + 2 * HPGQ_NUM_SCALARS;
-  // per mate [6][lmax] + hist + scalars, 16 B alignment, the byte-mask table,
-  // per wave and mate two read tables (2 x 1 KB) + segment ends (+ one list per
-  // extra scan) + the per-lane mean-quality sums, per wave a compaction scratch
-  // and a deferral word
-  const size_t lists = 1 + ((xm & hpgq::X_NOOR) ? 1 : 0) + ((xm & hpgq::X_LR) ? 1 : 0);
-  // (+ paired-end edit, first stage, no extra scans: the DMA rows of the next
-  // unit's trim windows, 3 x block x 16 B per mate, tri_body TDMA)
-  const bool tdma = p.edit_on && !follow && nm == 2 && xm == 0;
-  const size_t dma_words = tdma ? (size_t)nm * 3 * (size_t)block * 4 : 0;
-  const size_t st_words = (xm & hpgq::X_ST) ? (size_t)hpgq::kStWords : 0;   // (tri_body ST's shift buffers)
-  // (after the byte-mask table: the reciprocal table [pos + 1] of the epilogue's divisions)
-  return (size_t)nm * mate_words * 4 + 16 + 17 * 16 + ((size_t)pos + 1) * 4 +
-         (size_t)hpgq::kWaves * ((size_t)nm * (2 * 256 + 64 * lists + hpgq::kFxWords) + 64 + 4 + dma_words + st_words) * 4;
-}
+// the segmented kernels' selectors, one translation unit each, by geometry (GEO_*)
+static hpgq::KernelDesc (*const kSegKernel[3])(int nm, bool edit, int xm, bool follow) = {
+    hpgq::seg_kernel_tri, hpgq::seg_kernel_hex, hpgq::seg_kernel_wide};
 
-static size_t catch_all_lds(const hpgq_params_t &p, int nm) {
-  const size_t hlen = (size_t)p.lmax + 1 + HPGQ_MEANQ_BINS + HPGQ_GC_BINS;
-  const size_t hist_words = ((size_t)nm * hlen + 1) & ~(size_t)1;
-  return ((size_t)nm * 6 * p.lmax + hist_words) * 4 + (size_t)nm * HPGQ_NUM_SCALARS * 8 +
-         sizeof(hpgq::ColdParams) + (size_t)hpgq::kWaves * 64 * 4;
-}
-
-static int seg_block(int geo) {
-  return geo == hpgq::GEO_TRI ? hpgq::Geo<hpgq::GEO_TRI>::kBlock
-                              : (geo == hpgq::GEO_HEX ? hpgq::Geo<hpgq::GEO_HEX>::kBlock
-                                                      : hpgq::Geo<hpgq::GEO_WIDE>::kBlock);
-}
-
-static int seg_pos(int geo) {
-  return geo == hpgq::GEO_TRI ? hpgq::Geo<hpgq::GEO_TRI>::kPos
-                              : (geo == hpgq::GEO_HEX ? hpgq::Geo<hpgq::GEO_HEX>::kPos
-                                                      : hpgq::Geo<hpgq::GEO_WIDE>::kPos);
-}
-
-static bool seg_stage(Stage &s, int geo, int nm, bool edit, int xm, bool follow) {
-  hpgq::SegChoice ch{};
-  if (geo == hpgq::GEO_TRI) ch = hpgq::seg_kernel_tri(nm, edit, xm, follow, s.name, sizeof(s.name));
-  else if (geo == hpgq::GEO_HEX) ch = hpgq::seg_kernel_hex(nm, edit, xm, follow, s.name, sizeof(s.name));
-  else ch = hpgq::seg_kernel_wide(nm, edit, xm, follow, s.name, sizeof(s.name));
-  s.fn = ch.fn;
+// stage s runs kernel k: its LDS from the instance's own layout, its
+// persistent grid from the occupancy that leaves
+static int finish_stage(Stage &s, const hpgq::KernelDesc &k, int lmax, bool follow, int defer_len, int cus) {
+  if (!k.fn) return HPGQ_E_INVALID;
+  s.k = k;
   s.follow = follow;
-  s.block = seg_block(geo);
-  return ch.fn != nullptr;
-}
-
-static int finish_stage(hpgq_ctx *c, Stage &s, size_t lds, int cus) {
-  s.lds = lds;
+  s.defer_len = defer_len;
+  s.lds = k.lds_bytes(lmax);
   if (s.lds > 64 * 1024)
-    HPGQ_HIP_TRY(hipFuncSetAttribute(s.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
+    HPGQ_HIP_TRY(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds));
   int per_cu = 0;
-  HPGQ_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, s.fn, hpgq::kWG, s.lds));
+  HPGQ_HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, hpgq::kWG, s.lds));
   if (per_cu < 1) per_cu = 1;
   s.grid = cus * per_cu;   // persistent: every workgroup resident, grid-stride over units
   return HPGQ_OK;
@@ -319,10 +283,9 @@ static int plan_chain(hpgq_ctx *c, Chain &ch, int cus, int geo_force) {
   // extra per-step scans: N / out-of-range counts, window sums
   const int xm = (nx ? hpgq::X_NOOR : 0) | (lr ? hpgq::X_LR : 0);
   const bool edit = fl & hpgq::F_EDIT;
-  if ((c->route & 0xF) == HPGQ_ROUTE_CATCH_ALL) {   // the catch-all alone (tests)
-    catch_all(ch.s1, c->nm, p.lmax, needs_generic(fl), false);
-    return finish_stage(c, ch.s1, catch_all_lds(p, c->nm), cus);
-  }
+  ch.n = 0;
+  if ((c->route & 0xF) == HPGQ_ROUTE_CATCH_ALL)   // the catch-all alone (tests)
+    return finish_stage(ch.st[ch.n++], catch_all(c->nm, p.lmax, needs_generic(fl), false), p.lmax, false, INT_MAX, cus);
   // first geometry: hex for short reads; wide when the counters say reads are
   // 157..252 long (or when forced: adaptive wide-first chain, hpgq_debug_set_route)
   int geo = (stats && p.lmax > hpgq::Geo<hpgq::GEO_HEX>::kPos && p.lmax <= posw) ? hpgq::GEO_WIDE
@@ -338,23 +301,19 @@ static int plan_chain(hpgq_ctx *c, Chain &ch, int cus, int geo_force) {
   const bool st = false;   // (A/B builds: the unit-prologue trims)
 #endif
   const int xm1 = st ? hpgq::X_ST : xm;
-  if (!seg_stage(ch.s1, geo, c->nm, edit, xm1, false)) return HPGQ_E_INVALID;
-  const int pos1 = seg_pos(geo);
+  const hpgq::KernelDesc k1 = kSegKernel[geo](c->nm, edit, xm1, false);
   // a merged read longer than lmax leaves the segmented kernels (the
   // catch-all counts it as a long read)
-  ch.s1.defer_len = stats ? std::min(pos1, p.lmax) : pos1;
-  int rc = finish_stage(c, ch.s1, seg_lds(p, c->nm, xm1, pos1, false, seg_block(geo)), cus);
+  auto defer_len = [&](int pos) { return stats ? std::min(pos, p.lmax) : pos; };
+  int rc = finish_stage(ch.st[ch.n++], k1, p.lmax, false, defer_len(k1.pos), cus);
   if (rc) return rc;
-  ch.has2 = geo != hpgq::GEO_WIDE && ch.s1.defer_len < posw && !(stats && p.lmax <= pos1);
-  if (ch.has2) {
-    if (!seg_stage(ch.s2, hpgq::GEO_WIDE, c->nm, edit, xm, true)) return HPGQ_E_INVALID;
-    ch.s2.defer_len = stats ? std::min(posw, p.lmax) : posw;
-    rc = finish_stage(c, ch.s2, seg_lds(p, c->nm, xm, posw, true), cus);
+  // the wide follow-up, when reads may lie between the first geometry and it
+  if (geo != hpgq::GEO_WIDE && ch.st[0].defer_len < posw && !(stats && p.lmax <= k1.pos)) {
+    rc = finish_stage(ch.st[ch.n++], kSegKernel[hpgq::GEO_WIDE](c->nm, edit, xm, true), p.lmax, true,
+                      defer_len(posw), cus);
     if (rc) return rc;
   }
-  ch.has3 = true;
-  catch_all(ch.s3, c->nm, p.lmax, true, true);
-  return finish_stage(c, ch.s3, catch_all_lds(p, c->nm), cus);
+  return finish_stage(ch.st[ch.n++], catch_all(c->nm, p.lmax, true, true), p.lmax, true, INT_MAX, cus);
 }
 
 static int plan(hpgq_ctx *c, int cus) {
@@ -367,7 +326,7 @@ static int plan(hpgq_ctx *c, int cus) {
   if (rc) return rc;
   // hex first with a wide follow-up: batches of mostly long reads run better
   // wide first, so keep that chain too and choose per call
-  c->adaptive = c->ch[0].has2 && geo_force < 0 && !(c->route & HPGQ_ROUTE_NO_ADAPTIVE);
+  c->adaptive = c->ch[0].n == 3 && geo_force < 0 && !(c->route & HPGQ_ROUTE_NO_ADAPTIVE);
   if (!c->adaptive) return HPGQ_OK;
   rc = plan_chain(c, c->ch[1], cus, hpgq::GEO_WIDE);
   if (rc) return rc;
@@ -429,7 +388,7 @@ __global__ void __launch_bounds__(256) tail_bits_kernel(const int32_t *idx0, con
 
 extern "C" {
 
-const char *hpgq_kernel_name(const hpgq_ctx_t *ctx) { return ctx ? ctx->ch[0].s1.name : ""; }
+const char *hpgq_kernel_name(const hpgq_ctx_t *ctx) { return ctx ? ctx->ch[0].st[0].k.name : ""; }
 
 const char *hpgq_kernel_chain(const hpgq_ctx_t *ctx) {
   static thread_local char buf[700];
@@ -437,9 +396,8 @@ const char *hpgq_kernel_chain(const hpgq_ctx_t *ctx) {
   int o = 0;
   for (int k = 0; k < (ctx->adaptive ? 2 : 1); ++k) {
     const Chain &ch = ctx->ch[k];
-    o += std::snprintf(buf + o, sizeof(buf) - o, "%s%s%s%s%s%s", k ? " | adaptive: " : "", ch.s1.name,
-                       ch.has2 ? " -> " : "", ch.has2 ? ch.s2.name : "", ch.has3 ? " -> " : "",
-                       ch.has3 ? ch.s3.name : "");
+    for (int i = 0; i < ch.n; ++i)
+      o += std::snprintf(buf + o, sizeof(buf) - o, "%s%s", i ? " -> " : (k ? " | adaptive: " : ""), ch.st[i].k.name);
   }
   return buf;
 }
@@ -540,10 +498,8 @@ int hpgq_open(hpgq_ctx_t **out, int device, const hpgq_params_t *p) {
   }
   HPGQ_HIP_TRY(hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, device));
   rc = plan(c, c->cus);
-  if (rc == HPGQ_OK) {   // the long-read tail's second pass: the catch-all's follow-up instance
-    catch_all(c->redo, c->nm, p->lmax, true, true);
-    rc = finish_stage(c, c->redo, catch_all_lds(c->p, c->nm), c->cus);
-  }
+  if (rc == HPGQ_OK)   // the long-read tail's second pass: the catch-all's follow-up instance
+    rc = finish_stage(c->redo, catch_all(c->nm, p->lmax, true, true), p->lmax, true, INT_MAX, c->cus);
   if (rc) {
     hpgq_close(c);
     return rc;
@@ -596,7 +552,7 @@ void hpgq_close(hpgq_ctx_t *c) {
 
 // per-unit deferral masks for a batch of n reads
 static int ensure_bits(hpgq_ctx *c, int64_t n) {
-  const int block = std::min(c->ch[0].s1.block, c->adaptive ? c->ch[1].s1.block : INT_MAX);
+  const int block = std::min(c->ch[0].st[0].k.block, c->adaptive ? c->ch[1].st[0].k.block : INT_MAX);
   const size_t units = (size_t)((n + block - 1) / block) + 1;
   if (units <= c->bits_cap) return HPGQ_OK;
   HPGQ_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -617,12 +573,27 @@ static int stage_grid(const hpgq_ctx *c, const Stage &s) {
   return c->max_wg > 0 ? std::min(s.grid, c->max_wg) : s.grid;
 }
 
+// a follow-up stage's way in: the units of an earlier stage that hold a
+// deferred read (bits & and_bits, and_bits may be null), how many reads were
+// deferred to it, and the next call's counters it zeroes (bits null: the
+// stage takes the whole batch in units of its own block)
+static void units_in(hpgq::EngineArgs &A, const uint64_t *bits, const uint64_t *and_bits, int64_t nunits,
+                     int unit_reads, const uint32_t *pending, uint32_t *clear, uint32_t *clear2) {
+  A.unit_bits = bits;
+  A.unit_and = and_bits;
+  A.nunits = nunits;
+  A.unit_reads = unit_reads;
+  A.pending = pending;
+  A.pending_clear = clear;
+  A.pending_clear2 = clear2;
+}
+
 static int launch_stage(hpgq_ctx *c, const Stage &s, hpgq::EngineArgs &A) {
-  const int64_t units = s.follow ? A.nunits : (A.num_reads + s.block - 1) / s.block;
+  const int64_t units = s.follow ? A.nunits : (A.num_reads + s.k.block - 1) / s.k.block;
   const int64_t need = (units + hpgq::kWaves - 1) / hpgq::kWaves;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(need, stage_grid(c, s)));
   void *args[] = {&A};
-  HPGQ_HIP_TRY(hipLaunchKernel(s.fn, dim3(grid), dim3(hpgq::kWG), args, s.lds, c->stream));
+  HPGQ_HIP_TRY(hipLaunchKernel(s.k.fn, dim3(grid), dim3(hpgq::kWG), args, s.lds, c->stream));
   return HPGQ_OK;
 }
 
@@ -689,73 +660,45 @@ static int launch(hpgq_ctx *c, hpgq::EngineArgs &A, bool record) {
     c->calls.push_back(r);
   }
   c->reduced = false;
-  const int k = pick_chain(c);
-  const Chain &ch = c->ch[k];
-  if (!ch.has3) {   // the catch-all alone
-    A.unit_bits = A.unit_and = nullptr;
-    A.pending = A.pending_clear = A.pending_clear2 = nullptr;
-    A.defer_bits = nullptr;
-    A.defer_count = nullptr;
-    A.defer_len = INT_MAX;
-    return launch_stage(c, ch.s1, A);
-  }
-  int rc = ensure_bits(c, A.num_reads);
-  if (rc) return rc;
-  const int s = c->parity, o = s ^ 1;
-  c->parity = o;
-  uint32_t *f = c->d_flags;
-  // stage 1: every read; deferrals -> bits1, count -> PEND1[s]
-  hpgq::EngineArgs A1 = A;
-  A1.unit_bits = A1.unit_and = nullptr;
-  A1.pending = A1.pending_clear = A1.pending_clear2 = nullptr;
-  A1.defer_bits = c->d_bits1;
-  A1.defer_count = f + FL_PEND1 + s;
-  A1.defer_len = ch.s1.defer_len;
-  rc = launch_stage(c, ch.s1, A1);
-  if (rc) return rc;
-  const int64_t nunits = (A.num_reads + ch.s1.block - 1) / ch.s1.block;
-  const uint64_t *last_bits = c->d_bits1;
-  const uint32_t *last_count = f + FL_PEND1 + s;
-  uint32_t *last_clear = f + FL_PEND1 + o;
-  const uint64_t *and_bits = nullptr;
-  if (ch.has2) {   // stage 2: the deferred reads up to 252 bases; longer -> bits2, PEND2[s]
-    hpgq::EngineArgs A2 = A;
-    A2.unit_bits = c->d_bits1;
-    A2.unit_and = nullptr;
-    A2.nunits = nunits;
-    A2.unit_reads = ch.s1.block;
-    A2.pending = last_count;
-    A2.pending_clear = last_clear;
-    A2.pending_clear2 = nullptr;
-    A2.defer_bits = c->d_bits2;
-    A2.defer_count = f + FL_PEND2 + s;
-    A2.defer_len = ch.s2.defer_len;
-    A2.report = c->d_report;   // how many reads hex deferred: the next call's choice
-    A2.report_seq = ++c->seq;
-    if (!c->seq) A2.report_seq = ++c->seq;   // 0 means "no report yet"
-    c->rep_reads[c->seq & 15] = A.num_reads;
-    rc = launch_stage(c, ch.s2, A2);
+  const Chain &ch = c->ch[pick_chain(c)];
+  // deferred reads per first-stage unit and their counts by call parity: a
+  // stage's defer bits and count are the next stage's units and `pending`,
+  // which also zeroes the other parity's count for the next call
+  int s = 0, o = 0;
+  if (ch.n > 1) {
+    const int rc = ensure_bits(c, A.num_reads);
     if (rc) return rc;
-    and_bits = c->d_bits1;   // bits2 words are only written for units with bits1 set
-    last_bits = c->d_bits2;
-    last_count = f + FL_PEND2 + s;
-    last_clear = f + FL_PEND2 + o;
+    s = c->parity;
+    o = c->parity = s ^ 1;
   }
-  hpgq::EngineArgs A3 = A;   // stage 3: the catch-all, whatever is left
-  A3.unit_bits = last_bits;
-  A3.unit_and = and_bits;
-  A3.nunits = nunits;
-  A3.unit_reads = ch.s1.block;
-  A3.pending = last_count;
-  A3.pending_clear = last_clear;
-  // a chain without stage 2 (wide first) leaves PEND2 alone: clear the next
-  // call's, or a stale count from an earlier hex-first call of that parity
-  // makes its catch-all walk every unit
-  A3.pending_clear2 = ch.has2 ? nullptr : f + FL_PEND2 + o;
-  A3.defer_bits = nullptr;
-  A3.defer_count = nullptr;
-  A3.defer_len = INT_MAX;
-  return launch_stage(c, ch.s3, A3);
+  uint64_t *const bits[2] = {c->d_bits1, c->d_bits2};   // (after ensure_bits, which may reallocate them)
+  uint32_t *const pend[2] = {c->d_flags + FL_PEND1, c->d_flags + FL_PEND2};
+  const int block = ch.st[0].k.block;   // every follow-up stage walks the first stage's units
+  hpgq::EngineArgs S = A;
+  units_in(S, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr);   // the first stage: every read
+  for (int k = 0; k < ch.n; ++k) {
+    const bool last = k == ch.n - 1;
+    S.defer_bits = last ? nullptr : bits[k];
+    S.defer_count = last ? nullptr : pend[k] + s;
+    S.defer_len = last ? INT_MAX : ch.st[k].defer_len;
+    S.report = nullptr;
+    if (k == 1 && ch.n == 3) {   // behind hex / tri with a wide follow-up: how many reads it deferred
+      S.report = c->d_report;
+      S.report_seq = ++c->seq;
+      if (!c->seq) S.report_seq = ++c->seq;   // 0 means "no report yet"
+      c->rep_reads[c->seq & 15] = A.num_reads;
+    }
+    const int rc = launch_stage(c, ch.st[k], S);
+    if (rc || last) return rc;
+    // the next stage: this one's defer bits and count (a later stage's words
+    // are only written for units with bits[0] set).  A chain without a second
+    // follow-up (wide first) leaves PEND2 alone: clear the next call's, or a
+    // stale count from an earlier hex-first call of that parity makes its
+    // catch-all walk every unit
+    units_in(S, bits[k], k >= 1 ? bits[0] : nullptr, (A.num_reads + block - 1) / block, block, pend[k] + s,
+             pend[k] + o, ch.n == 2 ? pend[1] + o : nullptr);
+  }
+  return HPGQ_OK;
 }
 
 int hpgq_run_device(hpgq_ctx_t *c, const hpgq_batch_t *b, const hpgq_batch_t *b2,
@@ -1025,10 +968,8 @@ static int resolve(hpgq_ctx *c) {
     A.tail_hi = tail_hi(c);
     A.maxlen = f + FL_MAXLEN;
     A.need = f + FL_NEED;
-    A.unit_bits = c->d_bits1;
-    A.nunits = (r.n + 63) / 64;
-    A.unit_reads = 64;
-    A.pending = f + FL_REDO;
+    const int ub = c->redo.k.block;   // (64: the units tail_bits_kernel marked)
+    units_in(A, c->d_bits1, nullptr, (r.n + ub - 1) / ub, ub, f + FL_REDO, nullptr, nullptr);
     A.defer_len = INT_MAX;
     if ((rc = launch_stage(c, c->redo, A))) return rc;
   }
@@ -1271,15 +1212,12 @@ int hpgq_debug_stage_waves(const hpgq_ctx_t *c, int chain, int stage, int *waves
   if (!c || !waves || !unit_reads || chain < 0 || chain > (c->adaptive ? 1 : 0)) return HPGQ_E_INVALID;
   const Chain &ch = c->ch[chain];
   const Stage *s = nullptr;
-  int block = ch.s1.block;   // follow-up stages iterate over the first stage's units
-  switch (stage) {
-    case 1: s = &ch.s1; break;
-    case 2: s = ch.has2 ? &ch.s2 : nullptr; break;
-    case 3: s = ch.has3 ? &ch.s3 : nullptr; break;
-    case 4: s = &c->redo; block = 64; break;   // the long-read tail's second pass (resolve)
-    default: break;
-  }
-  if (!s || !s->fn) return HPGQ_E_INVALID;
+  int block = ch.st[0].k.block;   // follow-up stages iterate over the first stage's units
+  if (stage == 1) s = &ch.st[0];
+  else if (stage == 2 && ch.n == 3) s = &ch.st[1];            // the wide follow-up
+  else if (stage == 3 && ch.n >= 2) s = &ch.st[ch.n - 1];     // the catch-all follow-up
+  else if (stage == 4) s = &c->redo, block = c->redo.k.block;   // the long-read tail's second pass (resolve)
+  if (!s || !s->k.fn) return HPGQ_E_INVALID;
   *waves = stage_grid(c, *s) * hpgq::kWaves;
   *unit_reads = block;
   return HPGQ_OK;

@@ -39,58 +39,73 @@ constexpr int kStW = HPGQ_ST_WAVES;          // single-end edit, trims at the st
                                              // spilled VGPRs sit outside the group loop)
 constexpr const char *kGeoName = G == GEO_TRI ? "tri" : (G == GEO_HEX ? "hex" : "wide");
 
-template <bool F, int XM, bool EDIT>
-const void *x_kernel(int nm) {
-  return nm == 2 ? (const void *)engine_tri_x_kernel<kPeW, 2, G, F, XM, EDIT>
-                 : (const void *)engine_tri_x_kernel<EDIT ? kEdXW : kSeW, 1, G, F, XM, EDIT>;
+// the descriptor of ONE instance: everything the host needs comes from the
+// same template arguments as the kernel (its LDS bytes from its own layout)
+template <int MINW, int NM, bool EDIT, int XM, bool F>
+KernelDesc desc() {
+  KernelDesc d;
+  if constexpr (XM == 0) {
+    d.fn = (const void *)engine_tri_kernel<MINW, NM, EDIT, G, F>;
+    std::snprintf(d.name, sizeof(d.name), "hpgq::engine_tri_kernel<%d, %d, %s, %s%s>", MINW, NM,
+                  EDIT ? "edit" : "filter", kGeoName, F ? ", follow" : "");
+  } else {
+    d.fn = (const void *)engine_tri_x_kernel<MINW, NM, G, F, XM, EDIT>;
+    if constexpr (XM == X_ST)
+      std::snprintf(d.name, sizeof(d.name), "hpgq::engine_tri_kernel<%d, 1, edit, %s, st>", MINW, kGeoName);
+    else
+      std::snprintf(d.name, sizeof(d.name), "hpgq::engine_tri_x_kernel<%d, %d, %s%s%s%s%s>", MINW, NM, kGeoName,
+                    EDIT ? ", edit" : "", F ? ", follow" : "", (XM & X_NOOR) ? ", noor" : "",
+                    (XM & X_LR) ? ", window" : "");
+  }
+  d.block = Geo<G>::kBlock;
+  d.pos = Geo<G>::kPos;
+  d.lds_bytes = SegLds<NM, G, XM, EDIT, F>::bytes_for;
+  return d;
 }
 
+template <bool F, bool EDIT, int XM>
+KernelDesc inst(int nm) {
+  constexpr int kW1 = EDIT ? (XM || F ? kEdXW : kEdW) : kSeW;   // single-end waves per SIMD
+  return nm == 2 ? desc<kPeW, 2, EDIT, XM, F>() : desc<kW1, 1, EDIT, XM, F>();
+}
+
+// the instance for (nm, edit, xm) as a first (F false) or follow-up stage; fn
+// stays null when there is none
 template <bool F, bool EDIT>
-const void *x_kernel_for(int nm, int xm) {
-  return xm == X_NOOR ? x_kernel<F, X_NOOR, EDIT>(nm) : xm == X_LR ? x_kernel<F, X_LR, EDIT>(nm)
-                                                            : x_kernel<F, X_NOOR | X_LR, EDIT>(nm);
+KernelDesc pick_xm(int nm, int xm) {
+  switch (xm) {
+    case 0: return inst<F, EDIT, 0>(nm);
+    case X_NOOR: return inst<F, EDIT, X_NOOR>(nm);
+    case X_LR: return inst<F, EDIT, X_LR>(nm);
+    case X_NOOR | X_LR: return inst<F, EDIT, X_NOOR | X_LR>(nm);
+    case X_ST:   // single-end edit with the trims applied at the step (hex, first stage: tri_body ST)
+      if constexpr (G == GEO_HEX && !F && EDIT) {
+        if (nm == 1) return desc<kStW, 1, true, X_ST, false>();
+      }
+      break;
+    default: break;
+  }
+  return KernelDesc{};
 }
 
 template <bool F>
-SegChoice pick(int nm, bool edit, int xm, char *name, size_t cap) {
-  const void *fn = nullptr;
-  if (xm == X_ST) {   // single-end edit with the trims applied at the step (hex, first stage: tri_body ST)
-    if constexpr (G == GEO_HEX && !F) {
-      if (nm == 1 && edit) fn = (const void *)engine_tri_x_kernel<kStW, 1, G, false, X_ST, true>;
-    }
-    std::snprintf(name, cap, "hpgq::engine_tri_kernel<%d, 1, edit, %s, st>", kStW, kGeoName);
-    return SegChoice{fn, kStW};
-  }
-  const int w = nm == 2 ? kPeW : (edit ? (xm || F ? kEdXW : kEdW) : kSeW);
-  if (xm) {
-    fn = edit ? x_kernel_for<F, true>(nm, xm) : x_kernel_for<F, false>(nm, xm);
-    std::snprintf(name, cap, "hpgq::engine_tri_x_kernel<%d, %d, %s%s%s%s%s>", w, nm, kGeoName,
-                  edit ? ", edit" : "", F ? ", follow" : "", (xm & X_NOOR) ? ", noor" : "",
-                  (xm & X_LR) ? ", window" : "");
-  } else {
-    if (nm == 2) fn = edit ? (const void *)engine_tri_kernel<kPeW, 2, true, G, F>
-                           : (const void *)engine_tri_kernel<kPeW, 2, false, G, F>;
-    else if (edit) fn = (const void *)engine_tri_kernel<F ? kSeW : kEdW, 1, true, G, F>;
-    else fn = (const void *)engine_tri_kernel<kSeW, 1, false, G, F>;
-    std::snprintf(name, cap, "hpgq::engine_tri_kernel<%d, %d, %s, %s%s>", w, nm, edit ? "edit" : "filter", kGeoName,
-                  F ? ", follow" : "");
-  }
-  return SegChoice{fn, w};
+KernelDesc pick(int nm, bool edit, int xm) {
+  return edit ? pick_xm<F, true>(nm, xm) : pick_xm<F, false>(nm, xm);
 }
 
 }  // namespace
 
 #if HPGQ_GEO == 0
-SegChoice seg_kernel_tri(int nm, bool edit, int xm, bool follow, char *name, size_t cap) {
-  return follow ? SegChoice{nullptr, 0} : pick<false>(nm, edit, xm, name, cap);
+KernelDesc seg_kernel_tri(int nm, bool edit, int xm, bool follow) {
+  return follow ? KernelDesc{} : pick<false>(nm, edit, xm);
 }
 #elif HPGQ_GEO == 1
-SegChoice seg_kernel_hex(int nm, bool edit, int xm, bool follow, char *name, size_t cap) {
-  return follow ? SegChoice{nullptr, 0} : pick<false>(nm, edit, xm, name, cap);
+KernelDesc seg_kernel_hex(int nm, bool edit, int xm, bool follow) {
+  return follow ? KernelDesc{} : pick<false>(nm, edit, xm);
 }
 #else
-SegChoice seg_kernel_wide(int nm, bool edit, int xm, bool follow, char *name, size_t cap) {
-  return follow ? pick<true>(nm, edit, xm, name, cap) : pick<false>(nm, edit, xm, name, cap);
+KernelDesc seg_kernel_wide(int nm, bool edit, int xm, bool follow) {
+  return follow ? pick<true>(nm, edit, xm) : pick<false>(nm, edit, xm);
 }
 #endif
 

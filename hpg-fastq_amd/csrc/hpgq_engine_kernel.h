@@ -38,13 +38,13 @@
 //   * the workgroup epilogue adds its LDS partials into the ctx counters with
 //     one no-return u64 global atomic per nonzero entry (no slab, no fold).
 // All arithmetic is integer; results are bit-identical to the oracle.
+// Its LDS (and the segmented kernels') is laid out in hpgq_engine_lds.h.
 #pragma once
 #include "hpgq_common.h"
+#include "hpgq_engine_lds.h"
 
 namespace hpgq {
 
-constexpr int kWG = 256;
-constexpr int kWaves = kWG / 64;
 constexpr int kFlushEvery = 63;   // 6-bit base fields
 constexpr int kChunk = 252;       // positions per chunk (63 lanes x 4)
 
@@ -76,6 +76,7 @@ struct ColdParams {
   TrimSide tl, tr;   // the edit windows' in-range tests (segmented kernels' trim_finish)
   TrimSide to;       // the filter's quality range (segmented kernels' out-of-range count)
 };
+static_assert(sizeof(ColdParams) == kColdWords * 4, "the catch-all's LDS copy (hpgq_engine_lds.h)");
 
 struct EngineArgs {
   const char *seq[2];
@@ -119,6 +120,16 @@ struct EngineArgs {
   uint32_t *maxlen;       // atomicMax: the longest merged window longer than lmax
   uint32_t *need;         // atomicMax: a window longer than tail_hi (the tail was short)
   uint32_t *ovf;          // set to 1 when this call has such a window (nullptr: host path)
+};
+
+// one kernel instance as the host sees it (the segmented ones come from
+// hpgq_engine_geo.hip's pick, the catch-all's from hpgq_engine.hip)
+struct KernelDesc {
+  const void *fn = nullptr;
+  char name[80] = {0};                      // its signature (hpgq_kernel_name, hpgq_kernel_chain)
+  int block = 0;                            // reads per unit when it takes a whole batch
+  int pos = 0;                              // the longest read it holds
+  size_t (*lds_bytes)(int lmax) = nullptr;  // its layout's bytes() (hpgq_engine_lds.h)
 };
 
 // ---------------------------------------------------------------------------
@@ -829,24 +840,23 @@ __global__ void __launch_bounds__(kWG) engine_kernel(EngineArgs A) {
   const int lane = tid & 63;
   const int wave = uni(tid >> 6);
   const int lmax = A.lmax;
-  const int hlen = lmax + 1 + HPGQ_MEANQ_BINS + HPGQ_GC_BINS;
+  // every LDS region comes from the layout the host sizes the launch with (hpgq_engine_lds.h)
+  const CatchAllLds<NM> lay(lmax);
   constexpr int kCap = kChunk * NCH;   // positions the pipelined loads hold
   // lane l < 63 owns positions 4l.. of every chunk; lane 63 none
   const int lane_p0 = lane < 63 ? 4 * lane : 0x40000000;
   const uint32_t lane4 = 4u * (uint32_t)lane;
   const int ublock = FOLLOW ? A.unit_reads : 64;   // reads per unit
 
-  // LDS: pos_acc [NM][6][lmax] u32 | hist [NM][hlen] u32 | sc [NM][8] u64 | cold |
-  //      per wave: compaction scratch [64] u32
-  uint32_t *pos_acc = reinterpret_cast<uint32_t *>(lds);
-  uint32_t *hist = pos_acc + NM * 6 * lmax;
-  const int hist_words = (NM * hlen + 1) & ~1;
-  unsigned long long *sc = reinterpret_cast<unsigned long long *>(hist + hist_words);
-  ColdParams *cold = reinterpret_cast<ColdParams *>(sc + NM * HPGQ_NUM_SCALARS);
-  uint32_t *scratch = reinterpret_cast<uint32_t *>(cold + 1) + wave * 64;
-  for (int i = tid; i < NM * 6 * lmax + hist_words; i += kWG) pos_acc[i] = 0;
-  for (int i = tid; i < NM * HPGQ_NUM_SCALARS; i += kWG) sc[i] = 0;
-  if (tid < (int)(sizeof(ColdParams) / 4))
+  uint32_t *base = reinterpret_cast<uint32_t *>(lds);
+  auto sc = [&](int m) __attribute__((always_inline)) {
+    return reinterpret_cast<unsigned long long *>(lay.sc(base, m));
+  };
+  ColdParams *cold = reinterpret_cast<ColdParams *>(lay.cold(base));
+  uint32_t *scratch = lay.scratch(base, wave);
+  for (int i = tid; i < lay.partial_words(); i += kWG) base[i] = 0;
+  for (int i = tid; i < NM * HPGQ_NUM_SCALARS; i += kWG) sc(0)[i] = 0;
+  if (tid < kColdWords)
     reinterpret_cast<uint32_t *>(cold)[tid] = reinterpret_cast<const uint32_t *>(A.cold)[tid];
   __syncthreads();
 
@@ -981,7 +991,7 @@ __global__ void __launch_bounds__(kWG) engine_kernel(EngineArgs A) {
           if ((A.flags & F_STATS) && pass && lng[m]) {   // longer than lmax: merged by its own chunk loop
             ReadRef rw = shift_ref(rrs[m], out[m].ts);
             rw.n = out[m].wn;
-            long_merge<NM>(A, mb[m], rw, lane4, lane_p0, m, pos_acc + m * 6 * lmax, hist + m * hlen, fx16[m]);
+            long_merge<NM>(A, mb[m], rw, lane4, lane_p0, m, lay.pos_acc(base, m), lay.hist(base, m), fx16[m]);
           }
           // wn only feeds the histograms of reads <= lmax, so 16 bits suffice
           const uint32_t info = (uint32_t)min(out[m].wn, 0xFFFF) | ((uint32_t)pass << 16) |
@@ -993,7 +1003,7 @@ __global__ void __launch_bounds__(kWG) engine_kernel(EngineArgs A) {
         }
         if ((A.flags & F_STATS) && pass && ++since_flush == kFlushEvery) {
 #pragma unroll
-          for (int m = 0; m < NM; ++m) acc[m].flush(pos_acc + m * 6 * lmax, lmax, lane_p0);
+          for (int m = 0; m < NM; ++m) acc[m].flush(lay.pos_acc(base, m), lmax, lane_p0);
           since_flush = 0;
         }
       }
@@ -1042,7 +1052,7 @@ __global__ void __launch_bounds__(kWG) engine_kernel(EngineArgs A) {
         cnt[m][4] += (uint32_t)__builtin_popcountll(__ballot(pass));
         cnt[m][5] += (uint32_t)__builtin_popcountll(__ballot(pass && lg));
         if (pass && !lg) {
-          uint32_t *hm = hist + m * hlen;
+          uint32_t *hm = lay.hist(base, m);
           const uint32_t r1 = res_r1[m];
           const uint32_t s = r1 & 0x7FFFFu, gc = r1 >> 19, n = (uint32_t)wn;
           atomicAdd(&hm[n], 1u);
@@ -1071,12 +1081,12 @@ __global__ void __launch_bounds__(kWG) engine_kernel(EngineArgs A) {
   // ---- workgroup epilogue ---------------------------------------------------
   if (A.flags & F_TAIL_ONLY) return;   // (grid-uniform: nothing on chip to add)
 #pragma unroll
-  for (int m = 0; m < NM; ++m) acc[m].flush(pos_acc + m * 6 * lmax, lmax, lane_p0);
+  for (int m = 0; m < NM; ++m) acc[m].flush(lay.pos_acc(base, m), lmax, lane_p0);
 #pragma unroll
   for (int m = 0; m < NM; ++m) {
     const uint64_t tot = wave_sum64(fx16[m]);
     if (lane == 0) {
-      unsigned long long *scm = sc + m * HPGQ_NUM_SCALARS;
+      unsigned long long *scm = sc(m);
       if (cnt[m][0]) atomicAdd(&scm[HPGQ_S_NUM_INPUT], (unsigned long long)cnt[m][0]);
       if (cnt[m][1]) atomicAdd(&scm[HPGQ_S_NUM_PASSED], (unsigned long long)cnt[m][1]);
       if (cnt[m][2]) atomicAdd(&scm[HPGQ_S_NUM_FAILED], (unsigned long long)cnt[m][2]);
@@ -1087,12 +1097,10 @@ __global__ void __launch_bounds__(kWG) engine_kernel(EngineArgs A) {
     }
   }
   __syncthreads();
-  // (the compaction scratch is free now: pos_fix's wave totals)
-  uint32_t *wtot = reinterpret_cast<uint32_t *>(cold + 1);
-  for (int m = 0; m < NM; ++m) pos_fix<false>(pos_acc + m * 6 * lmax, hist + m * hlen, lmax, tid, wtot);
+  uint32_t *wtot = lay.pos_fix_wtot(base);
+  for (int m = 0; m < NM; ++m) pos_fix<false>(lay.pos_acc(base, m), lay.hist(base, m), lmax, tid, wtot);
   for (int m = 0; m < NM; ++m)
-    add_partials(A.counters + (size_t)m * A.clen, sc + m * HPGQ_NUM_SCALARS, hist + m * hlen, hlen,
-                 pos_acc + m * 6 * lmax, lmax, tid, kWG);
+    add_partials(A.counters + (size_t)m * A.clen, sc(m), lay.hist(base, m), lay.hlen, lay.pos_acc(base, m), lmax, tid, kWG);
 }
 
 }  // namespace hpgq

@@ -40,51 +40,23 @@
 //   * every read is accumulated; the epilogue decides pass/fail for the block
 //     vectorised over lanes and takes the failed reads back out.
 // The stats layout, histogram rules and counter epilogue are those of
-// engine_kernel, so all kernels of a chain add into one counter set.
+// engine_kernel, so all kernels of a chain add into one counter set.  The
+// geometries and every LDS region are in hpgq_engine_lds.h (SegLds).
 #pragma once
 #include "hpgq_engine_kernel.h"
 
 namespace hpgq {
 
-constexpr int kTriSlack = 8;    // readable bytes past the data end the loads may touch
+// readable bytes past the data end the loads may touch: the slack the ABI
+// asks every device batch to carry
+constexpr int kTriSlack = HPGQ_DEVICE_SLACK;
 
 // The unit epilogue reads each read's length and trim word back from the read
 // table (LDS) instead of holding them in VGPRs across the unit's steps (4 per
 // mate: current and next unit), which the paired-end edit kernel spilled
-// (TABLEN below; the follow-up stages keep them in registers).  The exact
-// mean-quality sum (u64 per lane and mate) accumulates in per-lane LDS slots
-// (one no-return ds_add_u64 per unit) instead of a VGPR pair held across the
-// loop: the paired-end edit kernel spilled exactly those pairs, a scratch
-// load + store per unit and mate (~200 MB of scratch writes per 10 M pairs).
-// (32 slots, lane & 31, since round 6: two lanes add into each, which frees
-// the LDS the reciprocal table takes without costing the paired-end edit
-// kernel its third workgroup per CU)
-constexpr int kFxSlots = 32;
-constexpr int kFxWords = 2 * kFxSlots;   // per wave and mate: kFxSlots u64
-
-constexpr int GEO_TRI = 0, GEO_HEX = 1, GEO_WIDE = 2;
-constexpr int X_NOOR = 1, X_LR = 2;   // extra filter scans (engine_tri_x_kernel)
-constexpr int X_ST = 4;               // single-end edit, trims applied at the step (tri_body ST)
-// ST: per wave, the step's raw seq and quality dwords of every lane (64 x 16 B
-// each, + 32 B read past the last lane), read back from a per-lane byte offset
-constexpr int kStWords = 2 * (64 * 4 + 8);
-
-// kBlock reads (<= 64: lane j <-> read j in the epilogue) in steps of kSegs
-// reads, kU steps per pipeline group, an even number of groups per block.
-template <int G>
-struct Geo;
-template <>
-struct Geo<GEO_TRI> {
-  static constexpr int kNW = 2, kSegs = 3, kSegW = 21, kOwn = 20, kBlock = 54, kU = 3, kPos = 160;
-};
-template <>
-struct Geo<GEO_HEX> {
-  static constexpr int kNW = 4, kSegs = 6, kSegW = 10, kOwn = 10, kBlock = 48, kU = 2, kPos = 156;
-};
-template <>
-struct Geo<GEO_WIDE> {   // 60-read blocks: read-table entry 63 stays empty (the padding steps' source)
-  static constexpr int kNW = 4, kSegs = 4, kSegW = 16, kOwn = 16, kBlock = 60, kU = 2, kPos = 252;
-};
+// (TABLEN below; the follow-up stages keep them in registers).  The
+// geometries (Geo<G>), the extra-scan bits (X_*) and every LDS region,
+// the per-lane mean-quality slots among them, are in hpgq_engine_lds.h.
 
 template <int G>
 constexpr uint64_t not_seg_first_mask() {   // lanes j with j % kSegs != 0
@@ -492,8 +464,9 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
   // the LDS partials cover lp positions: every read this kernel merges is at
   // most min(lmax, kPos) long (longer ones are deferred), so the counter set
   // on chip does not grow with lmax (at lmax 1024 it would cut the residency)
-  const int lp = min(lmax, Geo<G>::kPos);
-  const int hlen = lp + 1 + HPGQ_MEANQ_BINS + HPGQ_GC_BINS;
+  using L = SegLds<NM, G, XM, EDIT, FOLLOW>;
+  static_assert(L::NX == NX && L::LR == LR && L::ST == ST && L::TDMA == TDMA, "one derivation of the variant");
+  const int lp = L::positions(lmax);
   const int seg = min(lane / kSegW, kSegs);     // kSegs: idle lanes
   const int ls = lane - seg * kSegW;
   const bool owner = seg < kSegs && ls < GG::kOwn;
@@ -533,67 +506,42 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
   const int lo_r = A.min_q + A.phred, hi_r = A.max_q + A.phred;
   const int dlim = A.defer_len;   // longer reads go to the next stage
 
-  // LDS per mate: pos_acc [6][lmax] u32 | hist [hlen] u32 | sc [8] u64, then
-  // per wave: per mate two read tables [64] x 16 B (seq offset, qual offset,
-  // length | alignments, -) alternating between blocks, and segment ends [64]
-  // (+ [64] NX, + [64] LR), then a compaction scratch [64] u32 and a deferral word (u64,
-  // disjoint from the scratch: no type-punned aliasing); then the byte-mask table.
-  // (pos_acc row 5 holds "other" counts until the epilogue turns it into N)
-  const int hist_words = (hlen + 1) & ~1;
-  const int mate_words = 6 * lp + hist_words + 2 * HPGQ_NUM_SCALARS;   // even: sc 8-B aligned
+  // every LDS region comes from the layout the host sizes the launch with (hpgq_engine_lds.h)
+  const L lay(lmax);
   uint32_t *base = reinterpret_cast<uint32_t *>(lds);
-  auto pos_acc = [&](int m) __attribute__((always_inline)) { return base + m * mate_words; };
-  auto other = [&](int m) __attribute__((always_inline)) { return base + m * mate_words + 5 * lp; };
-  auto hist = [&](int m) __attribute__((always_inline)) { return base + m * mate_words + 6 * lp; };
+  auto pos_acc = [&](int m) __attribute__((always_inline)) { return lay.pos_acc(base, m); };
+  auto other = [&](int m) __attribute__((always_inline)) { return lay.other(base, m); };
+  auto hist = [&](int m) __attribute__((always_inline)) { return lay.hist(base, m); };
   auto sc = [&](int m) __attribute__((always_inline)) {
-    return reinterpret_cast<unsigned long long *>(base + m * mate_words + 6 * lp + hist_words);
+    return reinterpret_cast<unsigned long long *>(lay.sc(base, m));
   };
-  constexpr int kMateWaveWords = 2 * 256 + 64 * (1 + (NX ? 1 : 0) + (LR ? 1 : 0));
-  // TDMA: the next unit's trim windows, DMA'd one unit ahead (see dma_windows):
-  // per mate three rows (left, right 0, right 1) of kBlock x 16 B
-  constexpr int kDmaWords = TDMA ? NM * 3 * kBlock * 4 : 0;
-  constexpr int kWaveWords = NM * kMateWaveWords + 64 + 4 + NM * kFxWords + kDmaWords +
-                             (ST ? kStWords : 0);   // (multiple of 4: 16 B tables)
-  const int tab_words = (NM * mate_words + 3) & ~3;   // 16 B aligned (host: + 16 B)
-  // (ST: the shift buffers first in the wave's region, so their reads' offsets
-  // fit the ds_read2 offset fields)
-  uint32_t *wst = base + tab_words + wave * kWaveWords;
-  uint32_t *wtab = wst + (ST ? kStWords : 0);
-  auto tab = [&](int m, int tb) __attribute__((always_inline)) { return wtab + m * kMateWaveWords + tb * 256; };
-  auto wends = [&](int m) __attribute__((always_inline)) { return wtab + m * kMateWaveWords + 2 * 256; };
-  auto wends2 = [&](int m) __attribute__((always_inline)) { return wtab + m * kMateWaveWords + 2 * 256 + 64; };   // NX only
-  auto wends3 = [&](int m) __attribute__((always_inline)) {   // LR only
-    return wtab + m * kMateWaveWords + 2 * 256 + (NX ? 128 : 64);
-  };
-  uint32_t *scratch = wtab + NM * kMateWaveWords;
-  unsigned long long *dword = reinterpret_cast<unsigned long long *>(scratch + 64);   // 8 B aligned
-  // the DMA rows of mate m, window w (16 B aligned)
-  auto dma_row = [&](int m, int w) __attribute__((always_inline)) {
-    return scratch + 64 + 4 + NM * kFxWords + (m * 3 + w) * kBlock * 4;
-  };
-  // per-lane exact mean-quality sums, 8 B aligned
-  // ST: the wave's shift buffers (b = 0 seq, 1 quality; 16 B aligned)
-  auto stbuf = [&](int b) __attribute__((always_inline)) {
-    return wst + b * (kStWords / 2);
-  };
+  uint32_t *wreg = lay.wave(base, wave);   // this wave's region
+  auto tab = [&](int m, int tb) __attribute__((always_inline)) { return L::tab(wreg, m, tb); };
+  auto wends = [&](int m) __attribute__((always_inline)) { return L::ends(wreg, m); };
+  auto wends2 = [&](int m) __attribute__((always_inline)) { return L::ends2(wreg, m); };   // NX only
+  auto wends3 = [&](int m) __attribute__((always_inline)) { return L::ends3(wreg, m); };   // LR only
+  uint32_t *scratch = L::scratch(wreg);
+  unsigned long long *dword = reinterpret_cast<unsigned long long *>(L::dword(wreg));
+  auto dma_row = [&](int m, int w) __attribute__((always_inline)) { return L::dma_row(wreg, m, w); };   // TDMA
+  auto stbuf = [&](int b) __attribute__((always_inline)) { return L::stbuf(wreg, b); };                 // ST
   auto fxs = [&](int m) __attribute__((always_inline)) {
-    return reinterpret_cast<unsigned long long *>(scratch + 64 + 4 + m * kFxWords);
+    return reinterpret_cast<unsigned long long *>(L::fxs(wreg, m));
   };
 #pragma unroll
   for (int m = 0; m < NM; ++m)
     if (lane < kFxSlots) fxs(m)[lane] = 0ull;
   // byte masks by valid-byte count c = clamp(n - p0, 0, 4 NW): mtab[c][w]
   // (one LDS read per step instead of a clamp and a 64-bit shift per word)
-  uint32_t *mtab = base + tab_words + kWaves * kWaveWords;   // 16 B aligned
-  for (int i = tid; i < (4 * NW + 1) * NW; i += kWG) {
+  uint32_t *mtab = lay.mtab(base);
+  for (int i = tid; i < L::kMaskWords; i += kWG) {
     const int nb = min(max(i / NW - 4 * (i % NW), 0), 4);
     mtab[i] = nb == 4 ? 0xFFFFFFFFu : (1u << (8 * nb)) - 1u;
   }
   // the epilogue's divisions by a read's length n <= kPos as multiply-highs:
   // rtab[n] = ceil(2^32 / n) (0 for n = 1, see div_len)
-  uint32_t *rtab = mtab + 17 * 4;
-  for (int i = tid; i <= GG::kPos; i += kWG) rtab[i] = i <= 1 ? 0u : 0xFFFFFFFFu / (uint32_t)i + 1u;
-  for (int i = tid; i < NM * mate_words; i += kWG) base[i] = 0;
+  uint32_t *rtab = lay.rtab(base);
+  for (int i = tid; i < L::kRecipWords; i += kWG) rtab[i] = i <= 1 ? 0u : 0xFFFFFFFFu / (uint32_t)i + 1u;
+  for (int i = tid; i < lay.partial_words(); i += kWG) base[i] = 0;
   __syncthreads();
 
   // SRDs: the read bytes plus the load slack
@@ -1109,7 +1057,7 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
     const uint32_t sb = (uint32_t)(uintptr_t)scratch;   // (the rows sit at constant offsets from it)
     auto mate = [&](auto mtag) __attribute__((always_inline)) {
       constexpr int m = decltype(mtag)::value;
-      constexpr int kRow0 = 4 * (64 + 4 + NM * kFxWords + m * 3 * kBlock * 4), kRowB = 4 * kBlock * 4;
+      constexpr int kRow0 = 4 * (L::dma_row(0, m, 0) - L::scratch(0)), kRowB = 4 * L::kRowWords;
       const int off = bq[m] + ia[m], n = ie[m] - ia[m];
       int pa = off + n - 32;
       if (pa < 0) pa = 0;
@@ -1492,7 +1440,7 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
   }
   __syncthreads();
 #pragma unroll
-  for (int m = 0; m < NM; ++m) pos_fix<true>(pos_acc(m), hist(m), lp, tid, mtab);   // (mtab is free now)
+  for (int m = 0; m < NM; ++m) pos_fix<true>(pos_acc(m), hist(m), lp, tid, lay.pos_fix_wtot(base));
 #pragma unroll
   for (int m = 0; m < NM; ++m)
     add_partials_lp(A.counters + (size_t)m * A.clen, sc(m), hist(m), pos_acc(m), lmax, lp, tid, kWG);
@@ -1510,13 +1458,9 @@ __global__ void __launch_bounds__(kWG, MINW) engine_tri_x_kernel(EngineArgs A) {
 }
 
 // kernel selection (one translation unit per geometry, hpgq_engine_geo.hip):
-// the instance for (NM, edit, xm, follow) or nullptr; name gets its signature
-struct SegChoice {
-  const void *fn;
-  int min_waves;
-};
-SegChoice seg_kernel_tri(int nm, bool edit, int xm, bool follow, char *name, size_t cap);
-SegChoice seg_kernel_hex(int nm, bool edit, int xm, bool follow, char *name, size_t cap);
-SegChoice seg_kernel_wide(int nm, bool edit, int xm, bool follow, char *name, size_t cap);
+// the instance for (NM, edit, xm, follow); fn is null when there is none
+KernelDesc seg_kernel_tri(int nm, bool edit, int xm, bool follow);
+KernelDesc seg_kernel_hex(int nm, bool edit, int xm, bool follow);
+KernelDesc seg_kernel_wide(int nm, bool edit, int xm, bool follow);
 
 }  // namespace hpgq
