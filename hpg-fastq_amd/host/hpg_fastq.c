@@ -1,5 +1,5 @@
 /*
- * hpg_fastq.c — `hpg-fastq stats | filter | edit` on MI355X (libhpgq).
+ * hpg_fastq.c — `hpg-fastq stats | filter | edit | signature` on MI355X (libhpgq).
  *
  * Command dispatch and result printing after src/hpg-fastq.c and the
  * stats_fastq / filter_fastq / edit_fastq drivers (src/stats_fastq.c:424-500,
@@ -20,6 +20,7 @@ static void usage(const char *exec_name) {
   printf("Command: stats\t\tstatistics summary\n");
   printf("         filter\t\tfilter a FastQ file by using advanced criteria\n");
   printf("         edit\t\tedit a FastQ file according the specified options\n");
+  printf("         signature\tgenomic signature (--gs-filename file) of a FASTA reference\n");
   printf("\n");
   printf("For more information about a certain command, type %s <command> --help\n", exec_name);
   exit(-1);
@@ -28,6 +29,7 @@ static void usage(const char *exec_name) {
 int main(int argc, char **argv) {
   const char *exec_name = argv[0];
   if (argc == 1 || !strcmp(argv[1], "-h") || !strcmp(argv[1], "--help")) usage(exec_name);
+  if (!strcmp(argv[1], "signature")) return cli_signature(exec_name, argc - 1, argv + 1);
   int cmd;
   if (!strcmp(argv[1], "stats")) cmd = CMD_STATS;
   else if (!strcmp(argv[1], "filter")) cmd = CMD_FILTER;

@@ -89,4 +89,8 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res);
 /* src/stats_report.c: summary + data files (+ k-mer files when res->kmers) */
 int cli_report(const cli_options_t *o, const hpgq_params_t *p, const cli_result_t *res);
 
+/* `hpg-fastq signature` (hpgq_signature.c): FASTA -> genomic-signature file;
+ * argv[0] is the command name.  Returns the process exit code. */
+int cli_signature(const char *exec_name, int argc, char **argv);
+
 #endif

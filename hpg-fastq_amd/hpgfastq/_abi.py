@@ -79,6 +79,11 @@ class Summary(C.Structure):
                 ("num_T", C.c_uint64), ("num_N", C.c_uint64)]
 
 
+class GsInfo(C.Structure):
+    _fields_ = [("words", C.c_uint64), ("bases", C.c_uint64), ("ns", C.c_uint64),
+                ("sequences", C.c_uint64)]
+
+
 def counters_len(lmax):
     return NUM_SCALARS + (lmax + 1) + MEANQ_BINS + GC_BINS + 6 * lmax
 
@@ -147,6 +152,14 @@ _SIGS = [
     ("hpgq_cgr_write_pgm", C.c_int, [C.c_char_p, C.c_int, C.c_void_p, C.c_double]),
     ("hpgq_cgr_write_images", C.c_int, [C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_uint32, C.c_void_p]),
+    ("hpgq_gs_open", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]),
+    ("hpgq_gs_close", None, [C.c_void_p]),
+    ("hpgq_gs_add_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    ("hpgq_gs_add_host", C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
+    ("hpgq_gs_sync", C.c_int, [C.c_void_p]),
+    ("hpgq_gs_reset", C.c_int, [C.c_void_p]),
+    ("hpgq_gs_read", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GsInfo)]),
+    ("hpgq_gs_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
     ("hpgq_kmers_open", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p]),
     ("hpgq_kmers_close", None, [C.c_void_p]),
     ("hpgq_kmers_count_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p]),

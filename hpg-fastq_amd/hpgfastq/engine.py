@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (lib, check, Params, Batch, Summary, counters_len, CGR_ALL_READS, ROUTES)
+from ._abi import (lib, check, Params, Batch, Summary, GsInfo, counters_len, CGR_ALL_READS, ROUTES)
 
 # Kernel route for new Engines (tests / A/B: a key of ROUTES, or None for the
 # library's automatic chain).  Applied through hpgq_debug_set_route: the
@@ -361,6 +361,70 @@ class Kmers:
         out = np.zeros((1024, P.value), dtype=np.uint64)
         check(lib.hpgq_kmers_read_ext(self._h, _ptr(out), out.size, C.byref(P)), "hpgq_kmers_read_ext")
         return out
+
+
+class Signature:
+    """hpgq_gs: the genomic signature of FASTA text, the table
+    a --gs-filename file holds.  The text may be cut anywhere between add()s."""
+
+    def __init__(self, k, device=0, stream=None):
+        self.k = k
+        self.dim = 1 << k
+        self._h = None
+        h = C.c_void_p()
+        check(lib.hpgq_gs_open(C.byref(h), device, k, stream), "hpgq_gs_open")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib.hpgq_gs_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def add(self, text):
+        """bytes-like host text (staged; reusable on return) or a device uint8
+        tensor (async: keep it alive until sync(), table() or info())."""
+        if hasattr(text, "data_ptr"):
+            if not text.is_cuda or text.element_size() != 1 or not text.is_contiguous():
+                raise ValueError("device text must be a contiguous 1-byte tensor on the GPU")
+            check(lib.hpgq_gs_add_device(self._h, text.data_ptr() if text.numel() else None,
+                                         text.numel()), "hpgq_gs_add_device")
+        else:
+            b = bytes(text)
+            check(lib.hpgq_gs_add_host(self._h, b, len(b)), "hpgq_gs_add_host")
+
+    def sync(self):
+        check(lib.hpgq_gs_sync(self._h), "hpgq_gs_sync")
+
+    def reset(self):
+        check(lib.hpgq_gs_reset(self._h), "hpgq_gs_reset")
+
+    def set_max_workgroups(self, max_wg):
+        check(lib.hpgq_gs_debug_set_max_workgroups(self._h, max_wg),
+              "hpgq_gs_debug_set_max_workgroups")
+
+    def table(self):
+        """u32 [dim, dim], [co_x][co_y] (synchronises)."""
+        t = np.zeros(self.dim * self.dim, dtype=np.uint32)
+        check(lib.hpgq_gs_read(self._h, _ptr(t), None), "hpgq_gs_read")
+        return t.reshape(self.dim, self.dim)
+
+    def info(self):
+        """{'words', 'bases', 'ns', 'sequences'} (synchronises)."""
+        i = GsInfo()
+        check(lib.hpgq_gs_read(self._h, None, C.byref(i)), "hpgq_gs_read")
+        return {f: int(getattr(i, f)) for f, _ in GsInfo._fields_}
 
 
 def complete_prefix(buf, at_eof=False):

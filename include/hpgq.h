@@ -462,6 +462,49 @@ int  hpgq_cgr_write_images(const char *report_dir, const char *fq_path, int k,
                            const int32_t *table_dif);
 
 /* ---------------------------------------------------------------------- */
+/* genomic signature of a FASTA (what --gs-filename reads)                  */
+/* ---------------------------------------------------------------------- */
+
+/*
+ * Build-defined (the reference's generator is absent; lut_table_init,
+ * old/chaos_game.c:51-72, is what is left of it).  The text is
+ * a FASTA byte stream cut anywhere between calls.  '>' outside a header starts
+ * a header, which runs up to and including the next '\n', is ignored byte for
+ * byte, ends the current word and counts one sequence.  Outside headers
+ * A/C/G/T in either case are bases, N/n ends the current word, every other
+ * byte is skipped and does not end the word.  Every window of k consecutive
+ * bases is a word and adds 1 to table[co_x][co_y]: bit i of co_x (co_y) is dx
+ * (dy) of the window's i-th oldest base, dx = 1 for A/T, dy = 1 for G/T --
+ * the integer (int)f cell of old/chaos_game.c:201-251, not the carried double
+ * recurrence.  Cells are u32 and wrap; no cell exceeds info.words, so
+ * words < 2^32 means nothing wrapped.
+ */
+typedef struct hpgq_gs hpgq_gs_t;
+typedef struct hpgq_gs_info { uint64_t words, bases, ns, sequences; } hpgq_gs_info_t;
+
+/* 1 <= k <= 12 (else HPGQ_E_INVALID, before any device call); stream: the HIP
+ * stream to run on, or NULL for a stream of its own */
+int  hpgq_gs_open(hpgq_gs_t **gs, int device, int k, void *stream);
+void hpgq_gs_close(hpgq_gs_t *gs);
+/* Add n bytes (0 <= n < 2^31) of DEVICE text, async on the stream: the header
+ * flag, the word counter and the last k-1 bases live on the device, so no call
+ * waits for the GPU.  The text must stay valid until the stream has run it;
+ * any alignment. */
+int  hpgq_gs_add_device(hpgq_gs_t *gs, const char *text_dev, int64_t n);
+/* Add n bytes of HOST text (any n >= 0) through two page-locked 8 MB slots;
+ * the caller's buffer is reusable on return. */
+int  hpgq_gs_add_host(hpgq_gs_t *gs, const char *text, int64_t n);
+int  hpgq_gs_sync(hpgq_gs_t *gs);
+/* zero the table and the counts and forget the carried state (async) */
+int  hpgq_gs_reset(hpgq_gs_t *gs);
+/* table: dim*dim u32, row-major [co_x][co_y]; either output may be NULL (not
+ * both).  Synchronises the stream. */
+int  hpgq_gs_read(hpgq_gs_t *gs, uint32_t *table, hpgq_gs_info_t *info);
+/* Tests only: at most max_wg workgroups per kernel (0, the default: no limit),
+ * so that a small text gives every workgroup several tiles. */
+int  hpgq_gs_debug_set_max_workgroups(hpgq_gs_t *gs, int max_wg);
+
+/* ---------------------------------------------------------------------- */
 /* stats --kmers: 5-mer counts (src/stats_options.c:274, merge              */
 /* src/stats_fastq.c:384-410, report src/stats_report.c:492-563)            */
 /* ---------------------------------------------------------------------- */
