@@ -46,6 +46,7 @@ const char *hpgq_strerror(int code) {
     case HPGQ_E_STATE: return "invalid ctx state";
     case HPGQ_E_FORMAT: return "malformed FASTQ text";
     case HPGQ_E_IO: return "file i/o error";
+    case HPGQ_E_PAIRING: return "mate pairs out of step";
     default: return "unknown error";
   }
 }

@@ -48,6 +48,8 @@ int main(int argc, char **argv) {
   cli_result_t r;
   int rc = cli_run(o, &p, &r);
   if (rc) {
+    /* one line with the first bad pair (0-based, over the whole input), and the two names of a mismatch */
+    if (rc == HPGQ_E_PAIRING && r.pairing_msg[0]) fprintf(stderr, "hpg-fastq: pairing error at %s\n", r.pairing_msg);
     fprintf(stderr, "\nError: %s (%d)\n", hpgq_strerror(rc), rc);
     free(r.counters);
     cli_free(o);
@@ -75,13 +77,19 @@ int main(int argc, char **argv) {
       rc = 1;
     if (f) fclose(f);
   }
-  if (cmd == CMD_STATS && cli_report(o, &p, &r)) rc = 1;
+  if (cmd == CMD_STATS && !p.paired && cli_report(o, &p, &r)) rc = 1;
+  char mate_name[2][4096];
+  if (p.paired) cli_mate_names(o, mate_name);
+  /* paired input: one full report set per mate, from that mate's counter set */
+  for (int m = 0; cmd == CMD_STATS && p.paired && m < 2; ++m)
+    if (cli_report_set(o, &p, &r, counters + (size_t)m * hpgq_counters_len(r.lmax), mate_name[m])) rc = 1;
 
   if (!o->quiet) {
     printf("\n\nRESULTS\n");
     printf("=================================================\n");
     if (cmd == CMD_STATS) {
       printf("Report files were stored in '%s' directory\n", o->out_dirname);
+      if (p.paired) printf("\tMate 1: %s.*\n\tMate 2: %s.*\n", mate_name[0], mate_name[1]);
       if (p.filter_on) {
         printf("\nFiltering: enabled\n");
         printf("\tSo, statistics were computed for %lu of %lu reads.\n",
@@ -90,6 +98,14 @@ int main(int argc, char **argv) {
         printf("\nFiltering: disabled\n");
         printf("\tSo, statistics were computed for the whole input file.\n");
       }
+    } else if (p.paired) {
+      const char *ok = cmd == CMD_FILTER ? "passed" : "edit";
+      if (cmd == CMD_EDIT) printf("Num. edited reads : %lu (mate 1)\n", (unsigned long)r.num_edited);
+      printf("Num. passed pairs : %lu (%s/%s_1.fq, %s/%s_2.fq)\n", (unsigned long)r.num_passed, o->out_dirname, ok,
+             o->out_dirname, ok);
+      if (p.filter_on)
+        printf("Num. failed pairs : %lu (%s/failed_1.fq, %s/failed_2.fq)\n", (unsigned long)r.num_failed,
+               o->out_dirname, o->out_dirname);
     } else if (cmd == CMD_FILTER) {
       printf("Num. passed reads: %lu (%s/passed.fq)\n", (unsigned long)r.num_passed, o->out_dirname);
       printf("Num. failed reads: %lu (%s/failed.fq)\n", (unsigned long)r.num_failed, o->out_dirname);
@@ -104,9 +120,10 @@ int main(int argc, char **argv) {
     }
     if (r.writer)
       printf("Output writer     : %s\n", r.writer == 1 ? "mapped files, parallel copy" : "one stream writer thread");
-    printf("\nThroughput: %lu reads, %.3f GB of FastQ in %.3f s = %.2f Mreads/s (%d GPU worker%s)\n",
-           (unsigned long)r.num_reads, r.fastq_bytes / 1e9, r.seconds,
-           r.seconds > 0 ? r.num_reads / r.seconds / 1e6 : 0.0, r.num_gpus, r.num_gpus == 1 ? "" : "s");
+    printf("\nThroughput: %lu %s, %.3f GB of FastQ in %.3f s = %.2f M%s/s (%d GPU worker%s)\n",
+           (unsigned long)r.num_reads, p.paired ? "pairs" : "reads", r.fastq_bytes / 1e9, r.seconds,
+           r.seconds > 0 ? r.num_reads / r.seconds / 1e6 : 0.0, p.paired ? "pairs" : "reads", r.num_gpus,
+           r.num_gpus == 1 ? "" : "s");
     printf("=================================================\n");
   }
   free(r.counters);

@@ -24,7 +24,10 @@ typedef struct {
   int command;
   const char *command_name;
   const char *exec_name;
-  char *in_filename;
+  char *in_filename;        /* -f, or --fq1 */
+  char *in_filename2;       /* --fq2 (NULL: one input) */
+  int interleaved;          /* --interleaved: the mates alternate in -f */
+  int paired;               /* two mates per pair, either way */
   char *out_dirname;
   int num_threads;          /* reader threads */
   int batch_size;           /* accepted for compatibility; chunks are sized in bytes */
@@ -82,12 +85,25 @@ typedef struct {
   int cg_exact_calls;       /* chaos-game calls the exact simulation redid */
   int num_gpus;             /* GPU worker threads that ran */
   int writer;               /* filter / edit outputs: 1 mapped files (parallel copy), 2 stream writer */
+  /* HPGQ_E_PAIRING: the first pair out of step, counted over the whole input
+   * (-1: not known), and what the error line says after it */
+  int64_t bad_pair;
+  char pairing_msg[512];
 } cli_result_t;
 
 int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res);
 
-/* src/stats_report.c: summary + data files (+ k-mer files when res->kmers) */
+/* src/stats_report.c: summary + data files (+ k-mer files when res->kmers)
+ * from res->counters, named after the input's base name */
 int cli_report(const cli_options_t *o, const hpgq_params_t *p, const cli_result_t *res);
+/* the same from one counter set (layout of res->lmax) under `base`: paired
+ * input writes one report set per mate */
+int cli_report_set(const cli_options_t *o, const hpgq_params_t *p, const cli_result_t *res,
+                   const uint64_t *counters, const char *base);
+const char *cli_base_name(const char *path);
+/* the report base names of the two mates: each input's base name, or
+ * <base>_1 / <base>_2 for --interleaved (out: 2 x 4096 bytes) */
+void cli_mate_names(const cli_options_t *o, char out[2][4096]);
 
 /* `hpg-fastq signature` (hpgq_signature.c): FASTA -> genomic-signature file;
  * argv[0] is the command name.  Returns the process exit code. */

@@ -4,7 +4,8 @@
  * Same flags, defaults, validation and messages as the reference:
  * src/stats_options.c:15-300, src/filter_options.c:15-258,
  * src/edit_options.c:15-290; parse_range src/commons_fastq.c:31-103.
- * Build-specific additions: --gpu, --lmax, --chunk-mb, --print-params,
+ * Build-specific additions: --fq1 / --fq2 / --interleaved (paired-end input,
+ * after old/README), --gpu, --lmax, --chunk-mb, --print-params,
  * --counters-out, --kmers-out, --quiet.  --quality-encoding is accepted by every command
  * (quirk Q11).
  */
@@ -69,6 +70,9 @@ static void usage(const cli_options_t *o) {
          kCommandHelp[o->command]);
   printf("  -h, --help                      Help option\n");
   printf("  -f, --fastq-file=<file>         Input file name (FastQ format)\n");
+  printf("  --fq1, --fastq1=<file>          Paired-end input: mate 1 file (with --fq2, instead of -f)\n");
+  printf("  --fq2, --fastq2=<file>          Paired-end input: mate 2 file\n");
+  printf("  --interleaved                   Paired-end input: the mates alternate in the -f file\n");
   printf("  -o, --outdir=<file>             Output directory name\n");
   printf("  --num-threads=<int>             Number of threads (file readers)\n");
   printf("  --batch-size=<int>              Batch size (accepted; batches are --chunk-mb of text)\n");
@@ -133,7 +137,8 @@ static int count_arg(const cli_options_t *o, const char *flag, const char *s, in
 enum {
   O_THREADS = 1000, O_BATCH, O_QENC, O_KMERS, O_LRANGE, O_QRANGE, O_LLEN, O_LQRANGE, O_RLEN,
   O_RQRANGE, O_MAXN, O_MAXOOQ, O_GPU, O_LMAX, O_CHUNK, O_PRINT, O_COUNTERS, O_QUIET,
-  O_KMERSOUT, O_CG, O_KCG, O_GS, O_GPUS, O_CGBATCH, O_CGOUT, O_GPUW, O_STREAMW, O_WHOOK, O_COPYT, O_PFT
+  O_KMERSOUT, O_CG, O_KCG, O_GS, O_GPUS, O_CGBATCH, O_CGOUT, O_GPUW, O_STREAMW, O_WHOOK, O_COPYT, O_PFT,
+  O_FQ1, O_FQ2, O_INTER
 };
 
 cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **argv) {
@@ -158,6 +163,11 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   static const struct option longopts[] = {
       {"help", no_argument, 0, 'h'},
       {"fastq-file", required_argument, 0, 'f'},
+      {"fq1", required_argument, 0, O_FQ1},
+      {"fastq1", required_argument, 0, O_FQ1},
+      {"fq2", required_argument, 0, O_FQ2},
+      {"fastq2", required_argument, 0, O_FQ2},
+      {"interleaved", no_argument, 0, O_INTER},
       {"outdir", required_argument, 0, 'o'},
       {"num-threads", required_argument, 0, O_THREADS},
       {"batch-size", required_argument, 0, O_BATCH},
@@ -194,11 +204,15 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   if (argc < 2) usage(o);
   optind = 1;
   int c;
+  char *fq1 = NULL;
   while ((c = getopt_long(argc, argv, "hf:o:", longopts, NULL)) != -1) {
     switch (c) {
       case 'h': usage(o); break;
       case 'f': o->in_filename = strdup(optarg); break;
       case 'o': o->out_dirname = strdup(optarg); break;
+      case O_FQ1: fq1 = strdup(optarg); break;
+      case O_FQ2: o->in_filename2 = strdup(optarg); break;
+      case O_INTER: o->interleaved = 1; break;
       case O_THREADS: o->num_threads = atoi(optarg); break;
       case O_BATCH: o->batch_size = atoi(optarg); break;
       case O_QENC: o->quality_encoding_name = strdup(optarg); break;
@@ -244,8 +258,33 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
       default: usage(o);
     }
   }
+  /* paired-end input: --fq1 with --fq2, or --interleaved with -f */
+  if ((fq1 || o->in_filename2) && (o->in_filename || o->interleaved)) {
+    printf("\nError: --fq1/--fq2 cannot be combined with -f or --interleaved\n");
+    usage(o);
+  }
+  if ((fq1 != NULL) != (o->in_filename2 != NULL)) {
+    printf("\nError: --fq1 and --fq2 must be given together\n");
+    usage(o);
+  }
+  if (o->interleaved && !o->in_filename) {
+    printf("\nError: --interleaved needs the input file (-f)\n");
+    usage(o);
+  }
+  if (fq1) o->in_filename = fq1;
+  o->paired = o->in_filename2 != NULL || o->interleaved;
+  if (o->paired && (o->kmers_on || o->cg_on)) {
+    printf("\nError: --kmers and --cg are not available for paired-end input\n");
+    usage(o);
+  }
+  if (o->in_filename2 && command == CMD_STATS &&
+      strcmp(cli_base_name(o->in_filename), cli_base_name(o->in_filename2)) == 0) {
+    printf("\nError: --fq1 and --fq2 have the same base name (%s): the report files would collide\n",
+           cli_base_name(o->in_filename));
+    usage(o);
+  }
   /* validation, src/stats_options.c:108-160 */
-  if (!o->print_params && !exists(o->in_filename)) {
+  if (!o->print_params && (!exists(o->in_filename) || (o->in_filename2 && !exists(o->in_filename2)))) {
     printf("\nError: Input file name not found !\n");
     usage(o);
   }
@@ -336,7 +375,13 @@ void cli_display(const cli_options_t *o) {
   printf("=================================================\n");
   printf("Command name : %s\n", o->command_name);
   printf("\nMain options\n");
-  printf("\tFastQ input filename : %s\n", o->in_filename ? o->in_filename : "(none)");
+  if (o->in_filename2) {
+    printf("\tFastQ mate 1 filename: %s\n", o->in_filename);
+    printf("\tFastQ mate 2 filename: %s\n", o->in_filename2);
+  } else {
+    printf("\tFastQ input filename : %s\n", o->in_filename ? o->in_filename : "(none)");
+    if (o->interleaved) printf("\tPaired-end           : interleaved mates\n");
+  }
   printf("\tOutput dirname       : %s\n", o->out_dirname);
   printf("\tQuality encoding     : %s\n", o->quality_encoding_name);
   printf("\n%s options\n", o->command == CMD_EDIT ? "Edit and filter" : "Filter");
@@ -370,6 +415,16 @@ void cli_display(const cli_options_t *o) {
   printf("=================================================\n");
 }
 
+void cli_mate_names(const cli_options_t *o, char out[2][4096]) {
+  if (o->in_filename2) {
+    snprintf(out[0], 4096, "%s", cli_base_name(o->in_filename));
+    snprintf(out[1], 4096, "%s", cli_base_name(o->in_filename2));
+  } else {
+    snprintf(out[0], 4096, "%s_1", cli_base_name(o->in_filename));
+    snprintf(out[1], 4096, "%s_2", cli_base_name(o->in_filename));
+  }
+}
+
 static int dflt(int v, int d) { return v == HPGQ_NO_VALUE ? d : v; }
 
 void cli_params(const cli_options_t *o, hpgq_params_t *p) {
@@ -378,6 +433,7 @@ void cli_params(const cli_options_t *o, hpgq_params_t *p) {
   p->lmax = o->lmax;
   p->stats_on = o->command == CMD_STATS;
   p->filter_on = o->filter_on;
+  p->paired = o->paired;
   p->min_read_length = dflt(o->min_read_length, HPGQ_MIN_VALUE);
   p->max_read_length = dflt(o->max_read_length, HPGQ_MAX_VALUE);
   p->min_read_quality = dflt(o->min_read_quality, HPGQ_MIN_VALUE);
@@ -425,6 +481,7 @@ void cli_print_params(const hpgq_params_t *p) {
 void cli_free(cli_options_t *o) {
   if (!o) return;
   free(o->in_filename);
+  free(o->in_filename2);
   free(o->out_dirname);
   free(o->quality_encoding_name);
   free(o->read_length_range);

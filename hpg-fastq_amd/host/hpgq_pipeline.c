@@ -37,6 +37,16 @@
  *              are truncated to their final sizes at the end.  Otherwise
  *              (--stream-writer, or a map that fails) one writer thread
  *              writes the chunks in order.
+ *   paired     (--fq1 + --fq2, or --interleaved -f) the reader
+ *              fills a second page-locked text per chunk, counts each pread
+ *              piece's lines in its pread worker and cuts both texts at the
+ *              same record count (an interleaved text at an even one), each
+ *              side with its own carry; the worker parses both mates (or
+ *              splits the interleaved text on the device), checks the mate
+ *              names (hpgq_parse_pair_check) and makes one engine call over
+ *              the pairs; the stream writer writes passed_1/_2, failed_1/_2
+ *              (edit_1/_2).  A pair out of step ends the run with its number
+ *              over the whole input.
  * Stats never leave the device until the end (hpgq_read_counters).
  */
 #define _GNU_SOURCE
@@ -74,16 +84,34 @@ typedef struct {
   uint32_t *trim, *rec_start, *seq_start, *plus_start, *qual_start;
   int32_t *idx;
   size_t res_cap;
-  /* edit: the chunk's output records per class (0 edit.fq / passed, 1 failed),
-   * assembled by the GPU worker so the writer only writes them in order */
-  char *out[2];
-  size_t out_cap[2], out_len[2];
-  uint64_t out_n[2];
+  /* paired input: mate 2's text (--fq2; interleaved mates share buf) and the
+   * whole-input number of the chunk's first pair.  The results then hold both
+   * mates (mate_view): trim and idx one mate after the other, the record
+   * offsets per text */
+  char *buf2;
+  size_t len2, use2;
+  int64_t pair0;
+  /* edit: the chunk's output records per mate and class ([2 m + c]; c: 0
+   * edit.fq / passed, 1 failed), assembled by the GPU worker so the writer only
+   * writes them in order */
+  char *out[4];
+  size_t out_cap[4], out_len[4];
+  uint64_t out_n[4];
   /* mapped outputs: this chunk's copy parts (copy_part_t[MAX_COPIERS]) and
    * how many are still being copied (state 3 until the last one is done) */
   void *parts;
   int parts_left;
 } slot_t;
+
+/* paired input: one side of the reader (--fq1, --fq2; or the interleaved file) */
+typedef struct {
+  int fd;
+  off_t size, pos;
+  char *carry;
+  size_t carry_len;
+  int64_t carry_lines;   /* '\n' bytes in the carry */
+  const char *name;
+} side_t;
 
 typedef struct {
   const cli_options_t *o;
@@ -99,6 +127,13 @@ typedef struct {
   int64_t chunks;
   FILE *out_pass, *out_fail;
   uint64_t written_pass, written_fail;
+  /* paired input: the sides, mate 2's outputs ([0] passed_2 / edit_2, [1]
+   * failed_2; out_pass / out_fail are mate 1's) and the first pair out of step */
+  int nmates, nsides;
+  side_t side[2];
+  FILE *out2[2];
+  int64_t bad_pair, bad_chunk;
+  char pairing_msg[512];
   /* mapped outputs: [0] passed / edit.fq, [1] failed.fq (NULL: not written) */
   int mmap_out;
   mapout_t mo;           /* the mappings: reservation, prefault threads, SIGBUS guard */
@@ -186,6 +221,8 @@ typedef struct {
   size_t n;
   off_t off;
   ssize_t got;
+  int count;        /* paired reader: count the piece's lines here, in parallel */
+  int64_t lines;
 } pread_job_t;
 
 static void *pread_worker(void *arg) {
@@ -202,15 +239,26 @@ static void *pread_worker(void *arg) {
     done += (size_t)r;
   }
   j->got = (ssize_t)done;
+  if (j->count) j->lines = hpgq_fastq_count_lines(j->dst, (int64_t)done);
   return NULL;
 }
 
-/* read up to n bytes at P->pos with the reader threads */
-static ssize_t read_parallel(pipe_t *P, char *dst, size_t n) {
+/* a piece of a side's buffer and the lines that end in it */
+typedef struct {
+  size_t off, len;
+  int64_t lines;
+} piece_t;
+#define MAX_PIECES 66
+
+/* read up to n bytes of fd at pos with the reader threads; pc (paired reader):
+ * the pieces read, appended at pc[*npc], each with its line count */
+static ssize_t read_parallel_fd(pipe_t *P, int fd, off_t pos, char *dst, size_t n, const char *base, piece_t *pc,
+                                int *npc) {
   const int nt = P->o->num_threads;
   if (nt <= 1 || n < (4u << 20)) {
-    pread_job_t j = {P->fd, dst, n, P->pos, 0};
+    pread_job_t j = {fd, dst, n, pos, 0, pc != NULL, 0};
     pread_worker(&j);
+    if (pc && j.got > 0) pc[(*npc)++] = (piece_t){(size_t)(dst - base), (size_t)j.got, j.lines};
     return j.got;
   }
   pthread_t th[64];
@@ -221,7 +269,7 @@ static ssize_t read_parallel(pipe_t *P, char *dst, size_t n) {
   for (int i = 0; i < k; ++i) {
     const size_t a = (size_t)i * per;
     if (a >= n) break;
-    jobs[i] = (pread_job_t){P->fd, dst + a, (a + per > n ? n - a : per), P->pos + (off_t)a, 0};
+    jobs[i] = (pread_job_t){fd, dst + a, (a + per > n ? n - a : per), pos + (off_t)a, 0, pc != NULL, 0};
     pthread_create(&th[i], NULL, pread_worker, &jobs[i]);
     started++;
   }
@@ -230,10 +278,18 @@ static ssize_t read_parallel(pipe_t *P, char *dst, size_t n) {
   for (int i = 0; i < started; ++i) {
     pthread_join(th[i], NULL);
     if (jobs[i].got < 0) failed = 1;
-    if (!short_read && jobs[i].got > 0) total += jobs[i].got;
+    if (!short_read && jobs[i].got > 0) {
+      total += jobs[i].got;
+      if (pc) pc[(*npc)++] = (piece_t){(size_t)(jobs[i].dst - base), (size_t)jobs[i].got, jobs[i].lines};
+    }
     if (jobs[i].got < 0 || (size_t)jobs[i].got < jobs[i].n) short_read = 1;   /* EOF inside this piece */
   }
   return failed ? -1 : total;
+}
+
+/* read up to n bytes at P->pos with the reader threads */
+static ssize_t read_parallel(pipe_t *P, char *dst, size_t n) {
+  return read_parallel_fd(P, P->fd, P->pos, dst, n, dst, NULL, NULL);
 }
 
 static void reader_fail(pipe_t *P, int code) {
@@ -330,7 +386,216 @@ static void *reader_main(void *arg) {
   return NULL;
 }
 
+/* ---- paired reader ------------------------------------------------------- */
+
+/* A pairing error: keeps the lowest pair number reported, so
+ * that workers on different chunks agree on the first bad pair. */
+static void pairing_fail(pipe_t *P, int64_t chunk, int64_t pair, const char *msg) {
+  pthread_mutex_lock(&P->mu);
+  if (P->bad_pair < 0 || pair < P->bad_pair) {
+    P->bad_pair = pair;
+    P->bad_chunk = chunk;
+    snprintf(P->pairing_msg, sizeof(P->pairing_msg), "%s", msg);
+  }
+  if (!P->error) P->error = HPGQ_E_PAIRING;
+  pthread_cond_broadcast(&P->cv);
+  pthread_mutex_unlock(&P->mu);
+}
+
+/* The carry and a read of this side into buf: about `chunk` bytes in all, so
+ * the side with the shorter records, which carries more of them over every cut,
+ * reads less the next time and its carry does not grow.  pc: the pieces (the
+ * carry first), each with its line count from the pread workers. */
+static int fill_side(pipe_t *P, side_t *sd, char *buf, size_t cap, size_t chunk, size_t *len, piece_t *pc,
+                     int *npc) {
+  *npc = 0;
+  memcpy(buf, sd->carry, sd->carry_len);
+  if (sd->carry_len) pc[(*npc)++] = (piece_t){0, sd->carry_len, sd->carry_lines};
+  *len = sd->carry_len;
+  size_t want = sd->carry_len < chunk ? chunk - sd->carry_len : 0;
+  if (want > cap - 1 - *len) want = cap - 1 - *len;   /* 1 byte for a final newline */
+  if (want > 0 && sd->pos < sd->size) {
+    const ssize_t got = read_parallel_fd(P, sd->fd, sd->pos, buf + *len, want, buf, pc, npc);
+    if (got < 0) return HPGQ_E_IO;
+    sd->pos += got;
+    *len += (size_t)got;
+    if (got == 0) sd->size = sd->pos;   /* (the file shrank: its end is here) */
+  }
+  if (sd->pos >= sd->size && *len > 0 && buf[*len - 1] != '\n') {   /* the last line lacks its newline */
+    buf[(*len)++] = '\n';
+    pc[(*npc)++] = (piece_t){*len - 1, 1, 1};
+  }
+  return 0;
+}
+
+/* bytes of the first n records of buf, n <= the whole records in it: the pieces'
+ * line counts lead to the last piece that starts before record n's end, and
+ * hpgq_fastq_record_prefix counts on from the record start that follows it */
+static size_t cut_records(const char *buf, size_t len, const piece_t *pc, int npc, int64_t n) {
+  size_t anchor = 0;
+  int64_t before = 0, lines = 0;   /* whole records before the anchor; lines before piece p */
+  for (int p = 1; p < npc; ++p) {
+    lines += pc[p - 1].lines;
+    if ((lines + 3) / 4 >= n) break;
+    /* piece p starts inside line `lines`: (4 - lines % 4) % 4 newlines on, record ceil(lines / 4)
+     * starts; with lines % 4 == 0 the piece starts inside that record's first line, which counts
+     * the same for hpgq_fastq_record_prefix (it looks at newlines only) */
+    size_t a = pc[p].off;
+    for (int k = (int)((4 - lines % 4) % 4); k > 0 && a < len; --k) {
+      const char *nl = memchr(buf + a, '\n', len - a);
+      a = nl ? (size_t)(nl - buf) + 1 : len;
+    }
+    anchor = a;
+    before = (lines + 3) / 4;
+  }
+  int64_t got = 0;
+  return anchor + (size_t)hpgq_fastq_record_prefix(buf + anchor, (int64_t)(len - anchor), n - before, &got);
+}
+
+static int blank_only(const char *p, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (p[i] != '\n' && p[i] != '\r') return 0;
+  return 1;
+}
+
+static int64_t piece_lines(const piece_t *pc, int npc) {
+  int64_t t = 0;
+  for (int p = 0; p < npc; ++p) t += pc[p].lines;
+  return t;
+}
+
+/* The reader for paired input.  Two files: a chunk of each, each with its own
+ * carry, both cut at n = min(whole records in either); the rest of each side is
+ * carried.  --interleaved: one file, cut at an even record count.  At the end
+ * every side must be at EOF with nothing carried; otherwise the pairing error
+ * names the file that has records left.  pair0 of a chunk is the whole-input
+ * number of its first pair. */
+static void *reader_paired_main(void *arg) {
+  pipe_t *P = arg;
+  const int ns = P->nsides;
+  const size_t chunk = (size_t)P->o->chunk_mb << 20;
+  int64_t pairs = 0;
+  char msg[512];
+  for (int64_t k = 0;; ++k) {
+    slot_t *s = &P->slot[k % P->nslots];
+    pthread_mutex_lock(&P->mu);
+    while (s->state != 0 && !P->error) pthread_cond_wait(&P->cv, &P->mu);
+    const int err = P->error;
+    pthread_mutex_unlock(&P->mu);
+    if (err) break;
+    trace_at(P, k, 0, -1);
+    char *buf[2] = {s->buf, s->buf2};
+    size_t len[2] = {0, 0}, use[2] = {0, 0};
+    piece_t pc[2][MAX_PIECES];
+    int npc[2] = {0, 0}, eof[2] = {1, 1}, rc = 0;
+    int64_t lines[2] = {0, 0}, rec[2] = {0, 0};
+    for (int m = 0; m < ns && rc == 0; ++m) {
+      rc = fill_side(P, &P->side[m], buf[m], s->cap, chunk, &len[m], pc[m], &npc[m]);
+      eof[m] = P->side[m].pos >= P->side[m].size;
+      lines[m] = piece_lines(pc[m], npc[m]);
+      rec[m] = lines[m] / 4;
+    }
+    if (rc) {
+      reader_fail(P, rc);
+      break;
+    }
+    /* records per side in this chunk */
+    int64_t n = ns == 2 ? (rec[0] < rec[1] ? rec[0] : rec[1]) : rec[0] & ~(int64_t)1;
+    const int any_eof = eof[0] || (ns == 2 && eof[1]);
+    const int last = (eof[0] && eof[1]) || (n == 0 && any_eof);
+    if (n == 0 && !last) {
+      fprintf(stderr, "hpg-fastq: a record longer than --chunk-mb, or not FASTQ\n");
+      reader_fail(P, HPGQ_E_FORMAT);
+      break;
+    }
+    for (int m = 0; m < ns; ++m) {
+      side_t *sd = &P->side[m];
+      use[m] = n > 0 ? cut_records(buf[m], len[m], pc[m], npc[m], n) : 0;
+      sd->carry_len = len[m] - use[m];
+      sd->carry_lines = lines[m] - 4 * n;
+      memcpy(sd->carry, buf[m] + use[m], sd->carry_len);
+    }
+    /* at the end nothing may be left on either side (blank lines aside); the
+     * error is raised after the chunk's own pairs have gone to a worker, whose
+     * name check may find an earlier bad pair */
+    int tail_err = 0;
+    const int64_t npairs = pairs + (ns == 2 ? n : n / 2);
+    for (int m = 0; last && m < ns && !tail_err; ++m) {
+      const side_t *sd = &P->side[m];
+      if (sd->pos >= sd->size && blank_only(sd->carry, sd->carry_len)) continue;
+      if (rec[m] > n || sd->pos < sd->size) {   /* whole records without a mate */
+        if (ns == 2)
+          snprintf(msg, sizeof(msg), "pair %lld: %s has records left after the last record of %s",
+                   (long long)npairs, sd->name, P->side[1 - m].name);
+        else
+          snprintf(msg, sizeof(msg), "pair %lld: %s holds an odd number of records", (long long)npairs, sd->name);
+        tail_err = HPGQ_E_PAIRING;
+      } else {   /* a partial record at the end of the file */
+        tail_err = HPGQ_E_FORMAT;
+      }
+    }
+    s->len = len[0];
+    s->use = use[0];
+    s->len2 = len[1];
+    s->use2 = use[1];
+    s->eof = last;
+    s->pair0 = pairs;
+    pairs += ns == 2 ? n : n / 2;
+    trace_at(P, k, 1, -1);
+    pthread_mutex_lock(&P->mu);
+    s->chunk = k;
+    s->state = 1;
+    P->chunks = k + 1;
+    if (last) P->reader_done = 1;
+    pthread_cond_broadcast(&P->cv);
+    pthread_mutex_unlock(&P->mu);
+    if (tail_err == HPGQ_E_PAIRING) pairing_fail(P, k + 1, npairs, msg);
+    else if (tail_err) reader_fail(P, tail_err);
+    if (last) break;
+  }
+  pthread_mutex_lock(&P->mu);
+  P->reader_done = 1;
+  pthread_cond_broadcast(&P->cv);
+  pthread_mutex_unlock(&P->mu);
+  return NULL;
+}
+
 /* ---- writer ------------------------------------------------------------- */
+
+/* One mate's records in a processed slot.  Record i of the mate is record
+ * r = first + i * stride of its text (rs / ss / ps / qs: the record, sequence,
+ * '+' line and quality offsets of the text's `total` records); its trim and
+ * data_indices are at [i].  Single-end input is mate 0 with stride 1. */
+typedef struct {
+  const char *buf;
+  size_t use;
+  const uint32_t *rs, *ss, *ps, *qs, *trim;
+  const int32_t *idx;
+  int64_t total;
+  int first, stride;
+  FILE *f[2];   /* its outputs: [0] passed / edit, [1] failed */
+} mate_view_t;
+
+static mate_view_t mate_view(const pipe_t *P, const slot_t *s, int m) {
+  const int64_t n = s->nreads;
+  mate_view_t v = {s->buf, s->use, s->rec_start, s->seq_start, s->plus_start, s->qual_start, s->trim, s->idx,
+                   n, 0, 1, {P->out_pass, P->out_fail}};
+  if (P->nmates == 2) {
+    v.trim = s->trim + (size_t)m * n;
+    v.idx = s->idx + (size_t)m * (n + 1);
+    if (m) v.f[0] = P->out2[0], v.f[1] = P->out2[1];
+    if (P->nsides == 1) {   /* interleaved: records 2 i + m of the one text */
+      v.total = 2 * n;
+      v.first = m;
+      v.stride = 2;
+    } else if (m) {         /* mate 2's own text; its offsets follow mate 1's */
+      v.buf = s->buf2;
+      v.use = s->use2;
+      v.rs += n, v.ss += n, v.ps += n, v.qs += n;
+    }
+  }
+  return v;
+}
 
 static int write_span(FILE *f, const char *p, size_t n) { return fwrite(p, 1, n, f) == n ? 0 : -1; }
 
@@ -379,9 +644,12 @@ static int write_slot(pipe_t *P, slot_t *s) {
   const int edit = P->o->command == CMD_EDIT;
   const int filter_on = P->o->filter_on;
   if (edit) {   /* the worker assembled the trimmed records (assemble_edit) */
-    FILE *fc[2] = {P->out_pass, P->out_fail};
-    for (int c = 0; c < 2; ++c)
-      if (fc[c] && s->out_len[c] && write_span(fc[c], s->out[c], s->out_len[c])) return -1;
+    for (int m = 0; m < P->nmates; ++m) {
+      const mate_view_t v = mate_view(P, s, m);
+      for (int c = 0; c < 2; ++c)
+        if (v.f[c] && s->out_len[2 * m + c] && write_span(v.f[c], s->out[2 * m + c], s->out_len[2 * m + c]))
+          return -1;
+    }
     P->written_pass += s->out_n[0];
     P->written_fail += s->out_n[1];
     return 0;
@@ -391,28 +659,34 @@ static int write_slot(pipe_t *P, slot_t *s) {
    * (one write per span -- ~5 KB at 6 % failed reads -- ran at 4 GB/s into
    * tmpfs, which takes 8.6 GB/s in 64 KB writes) */
   static __thread spans_t S[2];
-  S[0].f = P->out_pass;
-  S[1].f = P->out_fail;   /* (without a filter every record is class 0) */
-  for (int c = 0; c < 2; ++c) {
-    S[c].n = 0;
-    if (S[c].f && fflush(S[c].f)) return -1;
-  }
-  for (int64_t i = 0; i < s->nreads; ++i) {
-    const int pass = s->mask[i] != 0;
-    spans_t *sp = &S[pass || !filter_on ? 0 : 1];
-    int64_t j = i + 1;
-    while (j < s->nreads && (s->mask[j] != 0) == pass) ++j;
-    if (sp->f) {
-      const uint32_t a = s->rec_start[i];
-      const uint32_t ee = j < s->nreads ? s->rec_start[j] : (uint32_t)s->use;
-      if (spans_add(sp, s->buf + a, ee - a)) return -1;
-      if (pass) P->written_pass += (uint64_t)(j - i);
-      else P->written_fail += (uint64_t)(j - i);
+  for (int m = 0; m < P->nmates; ++m) {
+    const mate_view_t v = mate_view(P, s, m);
+    S[0].f = v.f[0];
+    S[1].f = v.f[1];   /* (without a filter every record is class 0) */
+    for (int c = 0; c < 2; ++c) {
+      S[c].n = 0;
+      if (S[c].f && fflush(S[c].f)) return -1;
     }
-    i = j - 1;
+    for (int64_t i = 0; i < s->nreads; ++i) {
+      const int pass = s->mask[i] != 0;
+      spans_t *sp = &S[pass || !filter_on ? 0 : 1];
+      int64_t j = i + 1;   /* (interleaved mates: the other mate's record lies between) */
+      while (v.stride == 1 && j < s->nreads && (s->mask[j] != 0) == pass) ++j;
+      if (sp->f) {
+        const int64_t r0 = v.first + i * v.stride, r1 = v.first + (j - 1) * v.stride + 1;
+        const uint32_t a = v.rs[r0];
+        const uint32_t ee = r1 < v.total ? v.rs[r1] : (uint32_t)v.use;
+        if (spans_add(sp, v.buf + a, ee - a)) return -1;
+        if (m == 0) {
+          if (pass) P->written_pass += (uint64_t)(j - i);
+          else P->written_fail += (uint64_t)(j - i);
+        }
+      }
+      i = j - 1;
+    }
+    for (int c = 0; c < 2; ++c)
+      if (S[c].f && S[c].n && spans_flush(&S[c])) return -1;
   }
-  for (int c = 0; c < 2; ++c)
-    if (S[c].f && S[c].n && spans_flush(&S[c])) return -1;
   return 0;
 }
 
@@ -446,44 +720,48 @@ static void *writer_main(void *arg) {
  * to end against 135 for `stats` */
 static int assemble_edit(pipe_t *P, slot_t *s) {
   const int filter_on = P->o->filter_on;
-  FILE *fc[2] = {P->out_pass, P->out_fail};
-  for (int c = 0; c < 2; ++c) {
-    s->out_len[c] = 0;
-    s->out_n[c] = 0;
-    if (fc[c] && s->out_cap[c] < s->use + 64) {
-      free(s->out[c]);
-      s->out_cap[c] = s->use + s->use / 8 + 64;
-      s->out[c] = malloc(s->out_cap[c]);
-      if (!s->out[c]) {
-        s->out_cap[c] = 0;
-        return HPGQ_E_NOMEM;
+  for (int m = 0; m < P->nmates; ++m) {
+    const mate_view_t v = mate_view(P, s, m);
+    char **out = s->out + 2 * m;
+    for (int c = 0; c < 2; ++c) {
+      s->out_len[2 * m + c] = 0;
+      s->out_n[2 * m + c] = 0;
+      if (v.f[c] && s->out_cap[2 * m + c] < v.use + 64) {
+        free(out[c]);
+        s->out_cap[2 * m + c] = v.use + v.use / 8 + 64;
+        out[c] = malloc(s->out_cap[2 * m + c]);
+        if (!out[c]) {
+          s->out_cap[2 * m + c] = 0;
+          return HPGQ_E_NOMEM;
+        }
       }
     }
+    char *d[2] = {out[0], out[1]};
+    for (int64_t i = 0; i < s->nreads; ++i) {
+      const int c = s->mask[i] != 0 || !filter_on ? 0 : 1;
+      if (!v.f[c]) continue;
+      const int64_t r = v.first + i * v.stride;
+      const uint32_t a = v.rs[r];
+      const uint32_t ts = v.trim[i] & 0xFFFFu, te = v.trim[i] >> 16;
+      const uint32_t len = (uint32_t)(v.idx[i + 1] - v.idx[i]);
+      const uint32_t keep = len - ts - te;
+      const uint32_t hl = v.ss[r] - a, pl = v.qs[r] - v.ps[r];
+      char *o = d[c];
+      memcpy(o, v.buf + a, hl);                               /* header line */
+      o += hl;
+      memcpy(o, v.buf + v.ss[r] + ts, keep);
+      o += keep;
+      *o++ = '\n';
+      memcpy(o, v.buf + v.ps[r], pl);                         /* '+' line */
+      o += pl;
+      memcpy(o, v.buf + v.qs[r] + ts, keep);
+      o += keep;
+      *o++ = '\n';
+      d[c] = o;
+      s->out_n[2 * m + c]++;
+    }
+    for (int c = 0; c < 2; ++c) s->out_len[2 * m + c] = v.f[c] ? (size_t)(d[c] - out[c]) : 0;
   }
-  char *d[2] = {s->out[0], s->out[1]};
-  for (int64_t i = 0; i < s->nreads; ++i) {
-    const int c = s->mask[i] != 0 || !filter_on ? 0 : 1;
-    if (!fc[c]) continue;
-    const uint32_t a = s->rec_start[i];
-    const uint32_t ts = s->trim[i] & 0xFFFFu, te = s->trim[i] >> 16;
-    const uint32_t len = (uint32_t)(s->idx[i + 1] - s->idx[i]);
-    const uint32_t keep = len - ts - te;
-    const uint32_t hl = s->seq_start[i] - a, pl = s->qual_start[i] - s->plus_start[i];
-    char *o = d[c];
-    memcpy(o, s->buf + a, hl);                               /* header line */
-    o += hl;
-    memcpy(o, s->buf + s->seq_start[i] + ts, keep);
-    o += keep;
-    *o++ = '\n';
-    memcpy(o, s->buf + s->plus_start[i], pl);                 /* '+' line */
-    o += pl;
-    memcpy(o, s->buf + s->qual_start[i] + ts, keep);
-    o += keep;
-    *o++ = '\n';
-    d[c] = o;
-    s->out_n[c]++;
-  }
-  for (int c = 0; c < 2; ++c) s->out_len[c] = fc[c] ? (size_t)(d[c] - s->out[c]) : 0;
   return 0;
 }
 
@@ -499,13 +777,14 @@ static void free_results(slot_t *s) {
   s->res_cap = 0;
 }
 
-static int ensure_results(slot_t *s, int64_t n) {
+/* n reads (pairs), nm mates: the mask per read, everything else per mate */
+static int ensure_results(slot_t *s, int64_t n, int nm) {
   if ((size_t)n <= s->res_cap) return 0;
   free_results(s);
-  const size_t c = (size_t)n + (size_t)n / 4 + 1024;
+  const size_t c = (size_t)n + (size_t)n / 4 + 1024, cm = c * (size_t)nm;
   void **b[7] = {(void **)&s->mask, (void **)&s->trim, (void **)&s->rec_start, (void **)&s->seq_start,
                  (void **)&s->plus_start, (void **)&s->qual_start, (void **)&s->idx};
-  const size_t sz[7] = {c, c * 4, c * 4, c * 4, c * 4, c * 4, (c + 1) * 4};
+  const size_t sz[7] = {c, cm * 4, cm * 4, cm * 4, cm * 4, cm * 4, (cm + 2) * 4};
   for (int i = 0; i < 7; ++i)
     if (hpgq_host_alloc(b[i], sz[i])) {
       free_results(s);
@@ -773,6 +1052,7 @@ typedef struct {
   int w, device;
   hpgq_ctx_t *ctx;
   hpgq_parser_t *ps;
+  hpgq_parser_t *ps2;   /* --fq2: mate 2's parser, on the ctx stream too */
   hpgq_kmers_t *km;
   hpgq_cgr_t *cg;
   uint8_t *d_mask;
@@ -789,6 +1069,7 @@ static int worker_open(worker_t *W) {
   const cli_options_t *o = W->P->o;
   int rc = hpgq_open(&W->ctx, W->device, W->p);
   if (rc == 0) rc = hpgq_parser_open(&W->ps, W->device, hpgq_stream(W->ctx));
+  if (rc == 0 && W->P->nsides == 2) rc = hpgq_parser_open(&W->ps2, W->device, hpgq_stream(W->ctx));
   /* --kmers counts the reads the stats merge (passed ones when filtering,
    * src/stats_fastq.c:268-272,384-410) on the engine's stream, after it */
   if (rc == 0 && o->kmers_on) rc = hpgq_kmers_open(&W->km, W->device, W->p->lmax, hpgq_stream(W->ctx));
@@ -803,6 +1084,7 @@ static void worker_close(worker_t *W) {
   hpgq_device_free(W->d_mask);
   hpgq_device_free(W->d_trim);
   hpgq_parser_close(W->ps);
+  hpgq_parser_close(W->ps2);
   hpgq_kmers_close(W->km);
   hpgq_cgr_close(W->cg);
   hpgq_close(W->ctx);
@@ -839,7 +1121,7 @@ static int worker_chunk(worker_t *W, slot_t *s) {
   if (rc == 0 && W->km) rc = hpgq_kmers_count_device(W->km, &b, o->filter_on ? W->d_mask : NULL);
   if (rc == 0 && writes) {
     s->nreads = b.num_reads;
-    if (ensure_results(s, b.num_reads)) rc = HPGQ_E_NOMEM;
+    if (ensure_results(s, b.num_reads, 1)) rc = HPGQ_E_NOMEM;
     if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->mask, W->d_mask, (size_t)b.num_reads);
     if (rc == 0 && edit) {
       rc = hpgq_copy_to_host(W->ctx, s->trim, W->d_trim, (size_t)b.num_reads * 4);
@@ -861,6 +1143,86 @@ static int worker_chunk(worker_t *W, slot_t *s) {
   return rc;
 }
 
+/* the mate name of record r of a text, for the error line */
+static void record_name(const char *buf, size_t use, int64_t r, char *out, size_t cap) {
+  size_t a = (size_t)hpgq_fastq_record_prefix(buf, (int64_t)use, r, NULL) + 1, k = 0;   /* after '@' */
+  for (; a < use && k + 1 < cap; ++a) {
+    const char c = buf[a];
+    if (c == ' ' || c == '\t' || c == '\r' || c == '\n') break;
+    out[k++] = c;
+  }
+  out[k] = 0;
+}
+
+/* one chunk of paired input: both mates parsed (two texts, or one interleaved
+ * text split on the device), the mate names checked, one engine call over the
+ * pairs; for filter / edit the mask, both mates' trims, data_indices and record
+ * offsets come back */
+static int worker_chunk_paired(worker_t *W, slot_t *s) {
+  pipe_t *P = W->P;
+  const cli_options_t *o = P->o;
+  const int writes = o->command != CMD_STATS;
+  const int edit = o->command == CMD_EDIT;
+  const int two = P->nsides == 2;
+  hpgq_batch_t b1, b2;
+  s->nreads = 0;
+  int rc = two ? hpgq_parse_host(W->ps, s->buf, (int64_t)s->use, &b1)
+               : hpgq_parse_host_interleaved(W->ps, s->buf, (int64_t)s->use, &b1, &b2);
+  if (rc == 0 && two) rc = hpgq_parse_host(W->ps2, s->buf2, (int64_t)s->use2, &b2);
+  trace_at(P, s->chunk, 5, -1);
+  int64_t bad = -1;
+  if (rc == 0) rc = hpgq_parse_pair_check(W->ps, W->ps2, &bad);
+  if (rc == HPGQ_E_PAIRING) {
+    char msg[512], n1[160] = "", n2[160] = "";
+    if (bad >= 0 && bad < b1.num_reads && bad < b2.num_reads) {
+      record_name(s->buf, s->use, two ? bad : 2 * bad, n1, sizeof(n1));
+      record_name(two ? s->buf2 : s->buf, two ? s->use2 : s->use, two ? bad : 2 * bad + 1, n2, sizeof(n2));
+      snprintf(msg, sizeof(msg), "pair %lld: mate names differ: '%s' and '%s'", (long long)(s->pair0 + bad), n1, n2);
+    } else {
+      snprintf(msg, sizeof(msg), "pair %lld: the mates' record counts differ", (long long)(s->pair0 + (bad > 0 ? bad : 0)));
+    }
+    pairing_fail(P, s->chunk, s->pair0 + (bad > 0 ? bad : 0), msg);
+    return rc;
+  }
+  if (rc || b1.num_reads == 0) return rc;
+  const size_t n = (size_t)b1.num_reads;
+  if (n > W->dcap) {
+    hpgq_device_free(W->d_mask);
+    hpgq_device_free(W->d_trim);
+    W->d_mask = NULL;
+    W->d_trim = NULL;
+    W->dcap = n + n / 4 + 1024;
+    rc = hpgq_device_alloc(W->device, (void **)&W->d_mask, W->dcap);
+    if (rc == 0) rc = hpgq_device_alloc(W->device, (void **)&W->d_trim, W->dcap * 8);
+  }
+  if (rc == 0) {   /* the long-read tail for the longest record of either mate */
+    int64_t ml = hpgq_parser_max_length(W->ps);
+    if (two && hpgq_parser_max_length(W->ps2) > ml) ml = hpgq_parser_max_length(W->ps2);
+    rc = hpgq_reserve_length(W->ctx, ml);
+  }
+  if (rc == 0) rc = hpgq_run_device(W->ctx, &b1, &b2, writes ? W->d_mask : NULL, edit ? W->d_trim : NULL);
+  if (rc == 0 && writes) {
+    s->nreads = b1.num_reads;
+    if (ensure_results(s, b1.num_reads, 2)) rc = HPGQ_E_NOMEM;
+    if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->mask, W->d_mask, n);
+    if (rc == 0 && edit) {   /* (trim_out: mate 1 at [i], mate 2 at [n + i]) */
+      rc = hpgq_copy_to_host(W->ctx, s->trim, W->d_trim, n * 8);
+      if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->idx, b1.data_indices, (n + 1) * 4);
+      if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->idx + n + 1, b2.data_indices, (n + 1) * 4);
+    }
+    /* the record offsets: an interleaved text's 2 n in text order, else mate 2's after mate 1's */
+    if (rc == 0) rc = hpgq_parse_records(W->ps, s->rec_start, s->seq_start, s->plus_start, s->qual_start);
+    if (rc == 0 && two)
+      rc = hpgq_parse_records(W->ps2, s->rec_start + n, s->seq_start + n, s->plus_start + n, s->qual_start + n);
+  }
+  trace_at(P, s->chunk, 3, -1);
+  if (rc == 0) rc = hpgq_sync(W->ctx);
+  trace_at(P, s->chunk, 6, -1);
+  if (rc == 0 && edit) rc = assemble_edit(P, s);
+  W->num_reads += (uint64_t)b1.num_reads;
+  return rc;
+}
+
 static void *worker_main(void *arg) {
   worker_t *W = arg;
   pipe_t *P = W->P;
@@ -870,13 +1232,16 @@ static void *worker_main(void *arg) {
     pthread_mutex_lock(&P->mu);
     while (!(s->state == 1 && s->chunk == k) && !P->error && !(P->reader_done && k >= P->chunks))
       pthread_cond_wait(&P->cv, &P->mu);
-    const int stop = P->error || !(s->state == 1 && s->chunk == k);
+    /* (after a pairing error the chunks before it are still checked: the error
+     * line names the first bad pair of the whole input) */
+    const int stop = (P->error && !(P->error == HPGQ_E_PAIRING && k < P->bad_chunk)) ||
+                     !(s->state == 1 && s->chunk == k);
     pthread_mutex_unlock(&P->mu);
     if (stop) break;
     trace_at(P, k, 2, W->w);
-    const size_t use = s->use;   /* (s is the copiers' once place_and_copy handed it over) */
+    const size_t use = s->use + (P->nsides == 2 ? s->use2 : 0);   /* (s is the copiers' once place_and_copy handed it over) */
     int handed = 0;
-    int rc = worker_chunk(W, s);
+    int rc = P->nmates == 2 ? worker_chunk_paired(W, s) : worker_chunk(W, s);
     if (rc == 0 && writes && P->mmap_out) {
       rc = place_and_copy(P, s, &handed);   /* (an empty chunk is placed too: input order) */
     }
@@ -917,11 +1282,29 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   P.trace = getenv("HPGQ_TRACE") != NULL;
   P.o = o;
   memset(res, 0, sizeof(*res));
+  res->bad_pair = -1;
   P.fd = open(o->in_filename, O_RDONLY);
   if (P.fd < 0) return HPGQ_E_INVALID;
   struct stat st;
   fstat(P.fd, &st);
   P.size = st.st_size;
+  /* paired input: --fq1 + --fq2 are two sides, an --interleaved file one */
+  P.nmates = p->paired ? 2 : 1;
+  P.nsides = o->in_filename2 ? 2 : 1;
+  P.bad_pair = -1;
+  P.side[1].fd = -1;
+  if (p->paired) {
+    P.side[0] = (side_t){P.fd, P.size, 0, NULL, 0, 0, o->in_filename};
+    if (o->in_filename2) {
+      const int fd2 = open(o->in_filename2, O_RDONLY);
+      if (fd2 < 0 || fstat(fd2, &st)) {
+        if (fd2 >= 0) close(fd2);
+        close(P.fd);
+        return HPGQ_E_INVALID;
+      }
+      P.side[1] = (side_t){fd2, st.st_size, 0, NULL, 0, 0, o->in_filename2};
+    }
+  }
   pthread_mutex_init(&P.mu, NULL);
   pthread_cond_init(&P.cv, NULL);
   pthread_mutex_init(&P.cq_mu, NULL);
@@ -932,6 +1315,7 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   const int ndev = hpgq_device_count();
   if (ndev <= 0) {
     close(P.fd);
+    if (P.side[1].fd >= 0) close(P.side[1].fd);
     return HPGQ_E_NO_DEVICE;
   }
   const int ngpus = o->num_gpus > 0 ? o->num_gpus : ndev;
@@ -958,31 +1342,48 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   /* a chunk holds --chunk-mb of text (with --cg: one chaos-game batch) */
   size_t chunk = (size_t)o->chunk_mb << 20;
   if (P.cg_batch > 0 && (size_t)P.cg_batch > chunk) chunk = (size_t)P.cg_batch;
-  const double pinned_gb = (double)P.nslots * (double)(chunk + MAX_CARRY) / 1e9;
+  const double pinned_gb = (double)P.nslots * (double)P.nsides * (double)(chunk + MAX_CARRY) / 1e9;
   if (pinned_gb > 4.0)
     fprintf(stderr, "hpg-fastq: %d chunks of %zu MB: %.1f GB of page-locked host memory\n", P.nslots,
             (chunk + MAX_CARRY) >> 20, pinned_gb);
   for (int i = 0; i < P.nslots && rc == 0; ++i) {
     P.slot[i].cap = chunk + MAX_CARRY;
     rc = hpgq_host_alloc((void **)&P.slot[i].buf, P.slot[i].cap);
+    if (rc == 0 && P.nsides == 2) rc = hpgq_host_alloc((void **)&P.slot[i].buf2, P.slot[i].cap);
   }
   P.carry = malloc(MAX_CARRY + 16);
+  /* (a paired side carries whole records the other side had no mates for yet: up to a chunk) */
+  for (int m = 0; p->paired && m < P.nsides && rc == 0; ++m)
+    if (!(P.side[m].carry = malloc(chunk + MAX_CARRY))) rc = HPGQ_E_NOMEM;
   const int writes = o->command != CMD_STATS;
   const int edit = o->command == CMD_EDIT;
   if (rc == 0 && writes) {
     char path[4096];
     /* "w+": read + write, which a shared writable mapping needs (an O_WRONLY
      * descriptor cannot be mapped) */
-    snprintf(path, sizeof(path), "%s/%s.fq", o->out_dirname, edit ? "edit" : "passed");
+    /* paired input: passed_1.fq / passed_2.fq (edit_1 / edit_2), failed_1.fq / failed_2.fq */
+    snprintf(path, sizeof(path), "%s/%s%s.fq", o->out_dirname, edit ? "edit" : "passed", p->paired ? "_1" : "");
     P.out_pass = fopen(path, "w+");
     if (!edit || o->filter_on) {
-      snprintf(path, sizeof(path), "%s/failed.fq", o->out_dirname);
+      snprintf(path, sizeof(path), "%s/failed%s.fq", o->out_dirname, p->paired ? "_1" : "");
       P.out_fail = fopen(path, "w+");
     }
     if (!P.out_pass || ((!edit || o->filter_on) && !P.out_fail)) rc = HPGQ_E_INVALID;
     if (P.out_pass) setvbuf(P.out_pass, NULL, _IOFBF, 16 << 20);
     if (P.out_fail) setvbuf(P.out_fail, NULL, _IOFBF, 16 << 20);
-    if (rc == 0 && !o->stream_writer) {   /* not mappable (1): the writer thread */
+    if (p->paired) {
+      snprintf(path, sizeof(path), "%s/%s_2.fq", o->out_dirname, edit ? "edit" : "passed");
+      P.out2[0] = fopen(path, "w+");
+      if (!edit || o->filter_on) {
+        snprintf(path, sizeof(path), "%s/failed_2.fq", o->out_dirname);
+        P.out2[1] = fopen(path, "w+");
+      }
+      if (!P.out2[0] || ((!edit || o->filter_on) && !P.out2[1])) rc = HPGQ_E_INVALID;
+      for (int c = 0; c < 2; ++c)
+        if (P.out2[c]) setvbuf(P.out2[c], NULL, _IOFBF, 16 << 20);
+    }
+    /* (paired output goes through the stream writer: the mapped path is two-output) */
+    if (rc == 0 && !o->stream_writer && !p->paired) {   /* not mappable (1): the writer thread */
       const int m = map_outputs(&P);
       if (m < 0) rc = m;
     }
@@ -999,7 +1400,7 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   P.t0 = t0;
   if (P.mmap_out && (rc = start_copiers(&P))) goto done;
   pthread_t reader, writer;
-  pthread_create(&reader, NULL, reader_main, &P);
+  pthread_create(&reader, NULL, p->paired ? reader_paired_main : reader_main, &P);
   const int writer_thread = writes && !P.mmap_out;
   if (writer_thread) pthread_create(&writer, NULL, writer_main, &P);
   for (int w = 0; w < G; ++w) pthread_create(&W[w].th, NULL, worker_main, &W[w]);
@@ -1015,7 +1416,13 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   /* (the reader's and writer's generic -1 is HPGQ_E_INVALID; a copier's or the
    * prefault threads' HPGQ_E_IO stays what it is) */
   if (rc == 0 && P.error)
-    rc = P.error < 0 && P.error != HPGQ_E_FORMAT && P.error != HPGQ_E_IO ? HPGQ_E_INVALID : P.error;
+    rc = P.error < 0 && P.error != HPGQ_E_FORMAT && P.error != HPGQ_E_IO && P.error != HPGQ_E_PAIRING
+             ? HPGQ_E_INVALID
+             : P.error;
+  if (rc == HPGQ_E_PAIRING) {
+    res->bad_pair = P.bad_pair;
+    snprintf(res->pairing_msg, sizeof(res->pairing_msg), "%s", P.pairing_msg);
+  }
 
   /* the read-sharded merge: device counters, k-mer and CGR tables summed over
    * the workers (u64; CGR u32, which wraps like the reference's tables).  The
@@ -1098,14 +1505,19 @@ done:
   if (P.mmap_out) unmap_outputs(&P, &rc);
   if (P.out_pass) fclose(P.out_pass);
   if (P.out_fail) fclose(P.out_fail);
+  for (int c = 0; c < 2; ++c)
+    if (P.out2[c]) fclose(P.out2[c]);
   for (int i = 0; i < P.nslots; ++i) {
     hpgq_host_free(P.slot[i].buf);
+    hpgq_host_free(P.slot[i].buf2);
     free_results(&P.slot[i]);
     free(P.slot[i].parts);
-    free(P.slot[i].out[0]);
-    free(P.slot[i].out[1]);
+    for (int c = 0; c < 4; ++c) free(P.slot[i].out[c]);
   }
   free(P.carry);
+  free(P.side[0].carry);
+  free(P.side[1].carry);
+  if (P.side[1].fd >= 0) close(P.side[1].fd);
   free(P.cq);
   for (int w = 0; w < G; ++w) worker_close(&W[w]);
   close(P.fd);

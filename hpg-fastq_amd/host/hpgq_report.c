@@ -144,12 +144,19 @@ static int report_cg(const cli_options_t *o, const char *base, const cli_result_
   return rc;
 }
 
+const char *cli_base_name(const char *path) {
+  const char *slash = strrchr(path, '/');
+  return slash ? slash + 1 : path;
+}
+
 int cli_report(const cli_options_t *o, const hpgq_params_t *p, const cli_result_t *res) {
+  return cli_report_set(o, p, res, res->counters, cli_base_name(o->in_filename));
+}
+
+int cli_report_set(const cli_options_t *o, const hpgq_params_t *p, const cli_result_t *res, const uint64_t *c,
+                   const char *base) {
   /* the full-length set: every merged read at every position (res->lmax >= --lmax) */
-  const uint64_t *c = res->counters;
   const int lmax = res->lmax, phred = p->phred;
-  const char *slash = strrchr(o->in_filename, '/');
-  const char *base = slash ? slash + 1 : o->in_filename;
   hpgq_summary_t s;
   if (hpgq_counters_summary(c, lmax, &s)) return -1;
   const uint64_t *hl = c + hpgq_off_hist_len(lmax), *hq = c + hpgq_off_hist_meanq(lmax);

@@ -26,7 +26,9 @@ ROUTES = {"auto": ROUTE_AUTO, "single": ROUTE_CATCH_ALL, "tri": ROUTE_FIRST_TRI,
 
 ERRORS = {0: "ok", -1: "invalid argument", -2: "HIP runtime error", -3: "out of memory",
           -4: "read longer than lmax (not returned since round 6)", -5: "no HIP device", -6: "RCCL error",
-          -7: "invalid ctx state", -8: "malformed FASTQ text"}
+          -7: "invalid ctx state", -8: "malformed FASTQ text", -9: "file i/o error",
+          -10: "mate pairs out of step"}
+E_FORMAT, E_PAIRING = -8, -10
 
 
 class HpgqError(RuntimeError):
@@ -182,6 +184,14 @@ _SIGS = [
     ("hpgq_parse_records", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("hpgq_parser_stream", C.c_void_p, [C.c_void_p]),
     ("hpgq_parser_max_length", C.c_int64, [C.c_void_p]),
+    ("hpgq_fastq_record_prefix", C.c_int64, [C.c_char_p, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    ("hpgq_fastq_count_lines", C.c_int64, [C.c_char_p, C.c_int64]),
+    ("hpgq_parse_host_interleaved", C.c_int, [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(Batch),
+                                              C.POINTER(Batch)]),
+    ("hpgq_parse_device_interleaved", C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(Batch),
+                                                C.POINTER(Batch)]),
+    ("hpgq_parse_pair_check", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    ("hpgq_parser_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
     ("hpgq_device_count", C.c_int, []),
     ("hpgq_device_numa_node", C.c_int, [C.c_int]),
     ("hpgq_strerror", C.c_char_p, [C.c_int]),

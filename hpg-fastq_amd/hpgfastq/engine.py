@@ -9,7 +9,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (lib, check, Params, Batch, Summary, GsInfo, counters_len, CGR_ALL_READS, ROUTES)
+from ._abi import (lib, check, Params, Batch, Summary, GsInfo, counters_len, CGR_ALL_READS, ROUTES,
+                   E_PAIRING)
 
 # Kernel route for new Engines (tests / A/B: a key of ROUTES, or None for the
 # library's automatic chain).  Applied through hpgq_debug_set_route: the
@@ -432,6 +433,14 @@ def complete_prefix(buf, at_eof=False):
     return int(lib.hpgq_fastq_complete_prefix(buf, len(buf), 1 if at_eof else 0))
 
 
+def record_prefix(buf, max_records):
+    """hpgq_fastq_record_prefix: (bytes, records) of the first min(max_records,
+    whole records in `buf`) four-line records, counted from buf[0]."""
+    r = C.c_int64(0)
+    n = lib.hpgq_fastq_record_prefix(buf, len(buf), max_records, C.byref(r))
+    return int(n), int(r.value)
+
+
 class Parser:
     """hpgq_parser: FASTQ text -> device batch (parsing half of fastq_fread_se,
     src/stats_fastq.c:183, on the GPU)."""
@@ -465,6 +474,29 @@ class Parser:
         check(lib.hpgq_parse_host(self._h, text, len(text), C.byref(b)), "hpgq_parse_host")
         self.num_reads = int(b.num_reads)
         return b
+
+    def parse_interleaved(self, text):
+        """Host bytes of interleaved mates -> (mate 1, mate 2) device batches
+        (records 2i and 2i+1); records() then gives all records in text order."""
+        b1, b2 = Batch(), Batch()
+        check(lib.hpgq_parse_host_interleaved(self._h, text, len(text), C.byref(b1), C.byref(b2)),
+              "hpgq_parse_host_interleaved")
+        self.num_reads = 2 * int(b1.num_reads)
+        return b1, b2
+
+    def pair_check(self, other=None):
+        """hpgq_parse_pair_check over the last parse of this parser and `other`
+        (None: this parser's interleaved parse): -1 when every pair is in step,
+        else the first bad pair."""
+        bad = C.c_int64(-1)
+        rc = lib.hpgq_parse_pair_check(self._h, other._h if other is not None else None, C.byref(bad))
+        if rc != E_PAIRING:
+            check(rc, "hpgq_parse_pair_check")
+        return int(bad.value)
+
+    def set_max_workgroups(self, max_wg):
+        check(lib.hpgq_parser_debug_set_max_workgroups(self._h, max_wg),
+              "hpgq_parser_debug_set_max_workgroups")
 
     @property
     def max_length(self):

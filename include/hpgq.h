@@ -71,6 +71,8 @@ extern "C" {
 #define HPGQ_E_STATE           (-7)   /* call not valid in this ctx state     */
 #define HPGQ_E_FORMAT          (-8)   /* malformed FASTQ text                 */
 #define HPGQ_E_IO              (-9)   /* file open / read / write failed      */
+#define HPGQ_E_PAIRING        (-10)   /* mate pairs out of step: unequal or odd
+                                         record counts, or a name mismatch    */
 
 /* ---------------------------------------------------------------------- */
 /* batch                                                                  */
@@ -580,6 +582,51 @@ void *hpgq_parser_stream(hpgq_parser_t *ps);
 /* the longest record of the last parse (0 when empty): the engine's and the
  * k-mer counter's hpgq_*reserve_length before they run the batch */
 int64_t hpgq_parser_max_length(hpgq_parser_t *ps);
+
+/*
+ * Mate pairs.  Pair i is record i of two texts, or records 2i
+ * and 2i+1 of one interleaved text; the mates may differ in length.
+ *
+ * The mate name of a record is its header line's bytes after '@' up to, not
+ * including, the first space, tab, CR or LF.  If mate 1's name ends in "/1"
+ * and mate 2's in "/2" those two bytes are dropped from both (no other suffix
+ * pair is).  A pair is in step iff the two names then have the same length and
+ * bytes; two empty names are equal.
+ */
+
+/* Host only, HIP-free (csrc/hpgq_fastq_text.c).  A record is four
+ * '\n'-terminated lines counted from buf[0], which is a record start: the byte
+ * length of the first min(max_records, whole records present) records, their
+ * number in *records (may be NULL).  Nothing is validated: the GPU parser
+ * does that. */
+int64_t hpgq_fastq_record_prefix(const char *buf, int64_t n, int64_t max_records, int64_t *records);
+/* '\n' bytes in buf[0, n): the lines a reader's piece ends (host only) */
+int64_t hpgq_fastq_count_lines(const char *buf, int64_t n);
+
+/* Interleaved text: record 2i becomes read i of out1, record 2i+1 read i of
+ * out2, each with contiguous seq / quality of its own, data_indices starting
+ * at 0 and HPGQ_DEVICE_SLACK readable bytes past its end; both owned by the
+ * parser until its next parse.  One parse: the per-record lengths are scanned
+ * over the even and over the odd records and one copy pass routes each record
+ * to its mate.  An odd record count is HPGQ_E_PAIRING.  hpgq_parse_records then
+ * returns all 2 num_reads records in text order; hpgq_parser_max_length is the
+ * maximum over both mates. */
+int  hpgq_parse_host_interleaved(hpgq_parser_t *ps, const char *text, int64_t n, hpgq_batch_t *out1, hpgq_batch_t *out2);
+int  hpgq_parse_device_interleaved(hpgq_parser_t *ps, const char *text_dev, int64_t n, hpgq_batch_t *out1, hpgq_batch_t *out2);
+/* The mate-name rule over the last parses of ps1 and ps2 (record i of each),
+ * or with ps2 NULL over records 2i / 2i+1 of ps1's last, interleaved, parse
+ * (HPGQ_E_STATE when it was not).  HPGQ_OK with *first_bad = -1, or
+ * HPGQ_E_PAIRING with the lowest pair whose names differ, or min(n1, n2) when
+ * the names up to there agree and the record counts differ.  Both parsers
+ * are on one device, and the texts of their last parses must still be valid
+ * (the device text of hpgq_parse_device*; hpgq_parse_host* keeps its own copy
+ * until the next parse), as device batches must for hpgq_sync.  Runs on ps1's
+ * stream after waiting for ps2's, and synchronises it, as the parses do. */
+int  hpgq_parse_pair_check(hpgq_parser_t *ps1, hpgq_parser_t *ps2, int64_t *first_bad);
+/* Tests only: at most max_wg workgroups for the de-interleaving copy and the
+ * name check (0, the default: no limit), so that a small text gives every
+ * workgroup several iterations. */
+int  hpgq_parser_debug_set_max_workgroups(hpgq_parser_t *ps, int max_wg);
 
 /* ---------------------------------------------------------------------- */
 /* synthetic input (bench / tests): counter-based, identical on host & GPU */
