@@ -146,6 +146,40 @@ constexpr uint32_t kQFlip = 0x80808080u;
 constexpr int kQBias = 128;
 
 // ---------------------------------------------------------------------------
+// the read filter's bounds, per read
+// ---------------------------------------------------------------------------
+// The filter passes a read of length n with biased quality sum S iff
+//   (!filter) || (min_len <= n <= max_len && lo_r n <= S && S <= hi_r n)
+// (lo_r / hi_r: the biased mean bounds, min_q / max_q + phred + 128).  Only S
+// differs between the reads of one length, so the segmented kernels' unit
+// prologue folds the rest into two 16-bit bounds, lo16 | hi16 << 16 in the
+// read's record, and a step and the unit epilogue decide by lo16 <= S <= hi16
+// (in_filter_bounds): no multiply and no length compare per step.  Exact for
+// every S in [0, 65535], which holds every sum of a segmented read (at most
+// 252 bytes of at most 255).  A length out of range, a lower product above
+// 65535 or a negative upper product give the pair nothing passes (0xFFFF, 0);
+// the upper product is clamped to 65535, a negative lower one to 0; no filter
+// gives (0, 0xFFFF).  The products are taken in 64 bits: any int is safe.
+#ifndef HPGQ_HD
+#define HPGQ_HD __host__ __device__
+#endif
+constexpr uint32_t kBoundsAll = 0xFFFF0000u, kBoundsNone = 0x0000FFFFu;
+HPGQ_HD inline uint32_t filter_bounds(int n, int min_len, int max_len, int lo_r, int hi_r, bool filter) {
+  if (!filter) return kBoundsAll;
+  const long long lo = (long long)lo_r * n, hi = (long long)hi_r * n;
+  if (n < min_len || n > max_len || lo > 65535 || hi < 0) return kBoundsNone;
+  const uint32_t lo16 = lo < 0 ? 0u : (uint32_t)lo, hi16 = hi > 65535 ? 65535u : (uint32_t)hi;
+  return lo16 | (hi16 << 16);
+}
+HPGQ_HD inline bool in_filter_bounds(uint32_t bw, uint32_t S) { return (bw & 0xFFFFu) <= S && S <= (bw >> 16); }
+
+// The segmented kernels add a step's four biased quality bytes as one 32-bit
+// word, a += qm, beside the 16-bit pairs of bytes 1 and 3 (q13 += b1 | b3 <<
+// 16); the pairs of bytes 0 and 2 are then a - (q13 << 8) mod 2^32: exact
+// while each of the four per-position sums is below 2^16 (TriAcc).
+HPGQ_HD inline uint32_t quality_q02(uint32_t a, uint32_t q13) { return a - (q13 << 8); }
+
+// ---------------------------------------------------------------------------
 // SWAR + wave helpers
 // ---------------------------------------------------------------------------
 

@@ -18,7 +18,9 @@
 //   wide (G 2): 4 x 16 lanes x 16 B, reads <= 252, 60-read blocks (250 bp
 //               reads fill 98 % of the lanes)
 //   * the unit prologue writes one 16-byte record per read (dword-aligned seq
-//     and qual offsets, length | alignments) into a per-wave LDS table; each
+//     and qual offsets, length | alignments, and a spare dword: the trim word
+//     for edit, the read id in a follow-up stage, the read's filter bounds in
+//     the pass-first kernels) into a per-wave LDS table; each
 //     lane fetches its segment's record with ONE ds_read_b128, issues ONE
 //     buffer load per buffer and realigns with DPP wave_shl:1 + v_alignbyte
 //     (the last lane of a segment borrows from the next segment, which only
@@ -32,7 +34,8 @@
 //     count - A - C - G - T - other, count from the length histogram.
 //   * nibble counters (<= 15 steps) are widened into 8-bit per-base counters
 //     (<= 255 steps) and those flushed to LDS u32 arrays (ds_add); quality
-//     sums are 16-bit pairs of biased bytes (b ^ 0x80, hpgq_engine_kernel.h).
+//     sums are 16-bit pairs of biased bytes (b ^ 0x80, hpgq_engine_kernel.h),
+//     the pairs of positions 0,2 kept inside a full-word sum (TriAcc::qa).
 //   * per-read sums (biased quality | G+C << 18) use ONE inclusive DPP prefix scan
 //     for the wave; the last lane of each segment stores its segment end to
 //     LDS (no wait) and the block epilogue takes differences.  (Per wave at
@@ -99,13 +102,18 @@ template <int NW>
 struct TriAcc {
   uint32_t n4[NW][2];   // [word][C|G<<4, A|T<<4]: nibble per position
   uint32_t c8[NW][4];   // [word][A, C, G, T]: byte per position
-  uint32_t q02[NW], q13[NW];   // quality 16-bit pairs (positions 0,2 / 1,3 of the word)
+  // quality: qa adds the step's four biased bytes as ONE 32-bit word (no mask
+  // per step), q13 the 16-bit pairs of positions 1,3.  The pairs of positions
+  // 0,2 are qa - (q13 << 8) mod 2^32 (quality_q02), exact while each of the
+  // four per-position sums stays below 2^16: kByteEvery steps x 255 between
+  // flushes.  Subtractions (SubTag / UndoTag) take the same words back out.
+  uint32_t qa[NW], q13[NW];
   __device__ __forceinline__ void zero() {
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
       n4[w][0] = n4[w][1] = 0;
       c8[w][0] = c8[w][1] = c8[w][2] = c8[w][3] = 0;
-      q02[w] = q13[w] = 0;
+      qa[w] = q13[w] = 0;
     }
   }
   // nibbles -> bytes (every <= 15 steps and before any subtraction)
@@ -131,7 +139,8 @@ struct TriAcc {
     asm volatile("" : "+v"(p0), "+s"(lmax));
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
-      const uint32_t qv[4] = {q02[w] & 0xFFFFu, q13[w] & 0xFFFFu, q02[w] >> 16, q13[w] >> 16};
+      const uint32_t q02 = quality_q02(qa[w], q13[w]);
+      const uint32_t qv[4] = {q02 & 0xFFFFu, q13[w] & 0xFFFFu, q02 >> 16, q13[w] >> 16};
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int pos = p0 + 4 * w + i;
@@ -143,7 +152,7 @@ struct TriAcc {
         }
       }
       c8[w][0] = c8[w][1] = c8[w][2] = c8[w][3] = 0;
-      q02[w] = q13[w] = 0;
+      qa[w] = q13[w] = 0;
     }
   }
 };
@@ -481,6 +490,8 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
                          : TrimSide{0u, 0u, 0u, 0u};
   const bool x_hin = NX && trim_hi_none(xr);
   const int x_maxn = NX ? uni(A.cold->max_n) : 0, x_maxo = NX ? uni(A.cold->max_oor) : 0;
+  // (only a filter has the limits: the host sets these flags with F_FILTER
+  // alone, engine_flags, so the PF step's decision tests no `filter` of its own)
   const bool x_n = NX && (A.flags & F_NEED_N), x_o = NX && (A.flags & F_NEED_OOR);
   // LR: the window filters, read once (see NX above); length 0 = off
   const int w_ll = LR ? max(uni(A.cold->left_len), 0) : 0, w_rl = LR ? max(uni(A.cold->right_len), 0) : 0;
@@ -659,7 +670,11 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
       const uint32_t xq = live ? (uint32_t)(bq[m] + a) : 0x80000000u;
       // (FOLLOW: the read id rides in the record's spare dword, for the
       // epilogue; else the trim word, when the epilogue reads it back)
-      const uint32_t spare = FOLLOW ? rid : tw[m];
+      // (PF: the read's filter bounds lo16 | hi16 << 16, filter_bounds, for
+      // the steps' and the epilogue's pass/fail decision)
+      const uint32_t spare = FOLLOW ? rid
+                             : PF   ? filter_bounds((int)n, A.min_len, A.max_len, lo_r, hi_r, filter)
+                                    : tw[m];
       const v4u rec = v4u{xs & ~3u, xq & ~3u, n | ((xs & 3u) << 16) | ((xq & 3u) << 20), spare};
       *reinterpret_cast<v4u *>(tab(m, tb) + 4 * lane) = rec;
       len[m] = n;
@@ -942,19 +957,19 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
         if (UNDO) {   // the same values this step added: no nibble can underflow
           ac.n4[w][0] -= cg[w];
           ac.n4[w][1] -= at;
-          ac.q02[w] -= qm[w] & 0x00FF00FFu;
+          ac.qa[w] -= qm[w];
           ac.q13[w] -= h;
         } else if (SUB) {
           ac.c8[w][1] -= cg[w] & 0x0F0F0F0Fu;
           ac.c8[w][2] -= (cg[w] >> 4) & 0x0F0F0F0Fu;
           ac.c8[w][0] -= at & 0x0F0F0F0Fu;
           ac.c8[w][3] -= (at >> 4) & 0x0F0F0F0Fu;
-          ac.q02[w] -= qm[w] & 0x00FF00FFu;
+          ac.qa[w] -= qm[w];
           ac.q13[w] -= h;
         } else {
           ac.n4[w][0] += cg[w];
           ac.n4[w][1] += at;
-          ac.q02[w] += qm[w] & 0x00FF00FFu;
+          ac.qa[w] += qm[w];
           ac.q13[w] += h;
         }
       }
@@ -1030,13 +1045,14 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
     for (int w = 0; w < NW; ++w) {
       ac.n4[w][0] += sv.cg[w];
       ac.n4[w][1] += __builtin_amdgcn_perm(kATHi, kATLo, sv.cd[w]);
-      ac.q02[w] += sv.qm[w] & 0x00FF00FFu;
+      ac.qa[w] += sv.qm[w];
       ac.q13[w] += __builtin_amdgcn_perm(0u, sv.qm[w], 0x0C030C01u);   // bytes 1, 3
     }
   };
 
   uint32_t len[NM], lenn[NM];
   uint32_t tw[NM], twn[NM];   // EDIT: trim words of the lane's read (pair)
+  uint32_t fbw[NM];           // PF: the filter bounds of the lane's read (filter_bounds)
   uint64_t dm = 0, dmn = 0;   // deferred lanes of the current / next unit
   int tb = 0;   // read table of the current unit
   int32_t ia[NM], ie[NM];   // offsets of the unit after the next one to be described
@@ -1167,31 +1183,44 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
             }
           }
           if (PF && stats) {
-            bool pass = true;
-            if (filter) {   // this read's totals: the segment's last inclusive prefix minus its first exclusive one
-              const int sg = min(seg, kSegs - 1) * kSegW;
-              auto seg_total = [&](uint32_t Pi, uint32_t xi) __attribute__((always_inline)) {
-                return (uint32_t)__builtin_amdgcn_ds_bpermute(4 * (sg + kSegW - 1), (int)Pi) -
-                       (uint32_t)__builtin_amdgcn_ds_bpermute(4 * sg, (int)(Pi - xi));
-              };
-              const int n = (int)(grp[slot][u].n & 0xFFFFu), sraw = (int)(seg_total(P, x) & 0x3FFFFu);
-              pass = n >= A.min_len && n <= A.max_len && lo_r * n <= sraw && sraw <= hi_r * n;
-              if (NX) {
-                const uint32_t r2 = seg_total(P2, x2);
-                if (x_n && (int)(r2 & 0xFFFFu) > x_maxn) pass = false;
-                if (x_o && (int)(r2 >> 16) > x_maxo) pass = false;
-              }
-              if (LR) {
-                const uint32_t r3 = w_direct ? (uint32_t)__builtin_amdgcn_ds_bpermute(4 * sg, (int)x3) : seg_total(P3, x3);
-                const int kl = min(w_ll, n), kr = min(w_rl, n);
-                if (kl > 0 && !win_in((int)(r3 & 0xFFFFu), kl, w_lmin, w_lmax)) pass = false;
-                if (kr > 0 && !win_in((int)(r3 >> 16), kr, w_rmin, w_rmax)) pass = false;
-              }
+            // this read's totals: the segment's last inclusive prefix minus its first exclusive one
+            const int sg = min(seg, kSegs - 1) * kSegW;
+            auto seg_total = [&](uint32_t Pi, uint32_t xi) __attribute__((always_inline)) {
+              return (uint32_t)__builtin_amdgcn_ds_bpermute(4 * (sg + kSegW - 1), (int)Pi) -
+                     (uint32_t)__builtin_amdgcn_ds_bpermute(4 * sg, (int)(Pi - xi));
+            };
+            // the read's bounds from its record (filter_bounds, written by the
+            // unit prologue: length range, both products and `filter` are in
+            // them), the word the unit epilogue decides by too
+            const uint32_t bw = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(tab(m, tb)) +
+                                                                    step_off(t, nt) + 12u);
+            // (the sum is the total's low 16 bits: at most 252 x 255, G+C sits from bit 18 on)
+            bool pass = in_filter_bounds(bw, seg_total(P, x) & 0xFFFFu);
+            if (NX) {   // (x_n / x_o: only with a filter)
+              const uint32_t r2 = seg_total(P2, x2);
+              if (x_n && (int)(r2 & 0xFFFFu) > x_maxn) pass = false;
+              if (x_o && (int)(r2 >> 16) > x_maxo) pass = false;
+            }
+            if (LR && filter) {   // (the N / out-of-range + window kernel: the windows' lengths are the filter's)
+              const int n = (int)(grp[slot][u].n & 0xFFFFu);
+              const uint32_t r3 = w_direct ? (uint32_t)__builtin_amdgcn_ds_bpermute(4 * sg, (int)x3) : seg_total(P3, x3);
+              const int kl = min(w_ll, n), kr = min(w_rl, n);
+              if (kl > 0 && !win_in((int)(r3 & 0xFFFFu), kl, w_lmin, w_lmax)) pass = false;
+              if (kr > 0 && !win_in((int)(r3 >> 16), kr, w_rmin, w_rmax)) pass = false;
             }
             if (__builtin_expect(__ballot(sv.bad != 0) != 0, 0)) {   // rare: non-ACGTN bytes ("other" counts)
               uint32_t d2, d3;
               StepVals d;
-              if (pass) (void)account(MateTag<m>{}, grp[slot][u], true, AddTag{}, d2, d3, d);
+              // the step counted again from its raw words, behind an empty asm:
+              // hipcc otherwise shares this path's values with the step above
+              // and computes four of them (sw & 0x07070707) in EVERY step
+              // (not the N / out-of-range + window kernel: it spilled 4 more VGPRs)
+              TriPending<NW> pd = grp[slot][u];
+              if (!LR) {
+#pragma unroll
+                for (int w = 0; w < NW; ++w) asm volatile("" : "+v"(pd.s[w]), "+v"(pd.q[w]));
+              }
+              if (pass) (void)account(MateTag<m>{}, pd, true, AddTag{}, d2, d3, d);
             } else if (pass) {
               account_add(MateTag<m>{}, sv);
             }
@@ -1315,6 +1344,7 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
         const v2u r = *reinterpret_cast<const v2u *>(tab(m, tb) + 4 * lane + 2);
         len[m] = r.x & 0xFFFFu;
         tw[m] = EDIT ? r.y : 0u;
+        fbw[m] = PF ? r.y : 0u;
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -1329,7 +1359,9 @@ __device__ __forceinline__ void tri_body(const EngineArgs &A) {
       r1[m] = ends - (((not_seg_first >> lane) & 1u) ? prev : 0u);
       const int n = (int)len[m];
       const int sraw = (int)(r1[m] & 0x3FFFFu);
-      if (filter)
+      if (PF)   // the word the steps decided by: the mask and the counters rest on one predicate
+        pass = pass && in_filter_bounds(fbw[m], (uint32_t)sraw);
+      else if (filter)
         pass = pass && n >= A.min_len && n <= A.max_len && lo_r * n <= sraw && sraw <= hi_r * n;
       if (NX && filter) {
         const uint32_t e2 = inb ? wends2(m)[lane] : 0u;

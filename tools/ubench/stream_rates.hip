@@ -7,7 +7,8 @@
 //   hex    6 reads per step, 10 lanes x 16 B of a 150-byte read
 // Each lane XOR-folds what it loads (kept alive through one store per lane).
 //   units  the hex kernel's unit / group issue order and load policies (k_units;
-//          `./stream_rates units [chain ...]` runs only these)
+//          `./stream_rates units [chain ...]` runs only these; `units check`
+//          compares the byte-exact loads' bytes with the dword-rounded ones')
 //   hipcc --offload-arch=gfx950 -O3 stream_rates.hip -o stream_rates && ./stream_rates
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -134,11 +135,21 @@ __global__ void __launch_bounds__(kWG) k_reads(const char *a, const char *b, uin
 // BEFORE the group's stream loads (one lane per buffer loads, plain policy,
 // the first dword of the NEXT group's first read; the other lanes pass an
 // out-of-range offset: zeros, no traffic); 3 the same touch AFTER them; 4 no
-// touch, the group's last step plain and its first nt.
+// touch, the group's last step plain and its first nt; 5 as 4, but every lane
+// loads from its read's EXACT byte offset (no rounding to a dword, so the
+// consumer needs no DPP move and no v_alignbyte to realign).
+// CHK (`units check`): instead of the fold and the chain, every step's bytes
+// are realigned as the kernel does (V < 5: the offset's low two bits, lane +
+// 1's first dword, v_alignbyte; V 5: as loaded), masked to the read's kL
+// bytes and summed (v_sad_u8); out gets per thread the sum weighted by the
+// lane's place in its read (1 .. 10) and the plain sum.  On patterned data
+// the two variants' totals must be equal, and the plain one the sum of all
+// bytes: this shows that buffer loads honour byte offsets here.
 constexpr int kUR = 48, kUS = 6, kUG = 2;   // reads per unit, per step; steps per group
-template <int V>
+template <int V, bool CHK = false>
 __global__ void __launch_bounds__(kWG, 4) k_units(const char *a, const char *b, uint32_t n, const int32_t *idx,
                                                   int64_t nreads, uint32_t *out, int chain) {
+  constexpr bool EXACT = V == 5;
   __shared__ uint32_t tabs[kWG / 64][2][64];
   const auto ra = rsrc(a, n + 64), rb = rsrc(b, n + 64);
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -156,11 +167,12 @@ __global__ void __launch_bounds__(kWG, 4) k_units(const char *a, const char *b, 
   };
   uint32_t ahead = 0;
   auto describe = [&](int64_t un, int tb) {
-    tabs[w][tb][lane] = ahead & ~3u;
+    tabs[w][tb][lane] = (EXACT || CHK) ? ahead : ahead & ~3u;
     __builtin_amdgcn_wave_barrier();
     ahead = fetch(un + nw);
   };
   v4u ps[2][kUG], pq[2][kUG];
+  uint32_t al[2][kUG];   // CHK: the offsets' low two bits
   uint32_t tk[2][2] = {{0u, 0u}, {0u, 0u}};
   auto touch = [&](int tb, int g, int slot) {
     const bool lastg = g == kUR / (kUS * kUG) - 1;
@@ -173,8 +185,10 @@ __global__ void __launch_bounds__(kWG, 4) k_units(const char *a, const char *b, 
     if (V == 2) touch(tb, g, slot);
 #pragma unroll
     for (int s = 0; s < kUG; ++s) {
-      const uint32_t o = tabs[w][tb][kUS * (g * kUG + s) + seg] + lane16;
-      if (V == 0 || (V == 4 && s == kUG - 1)) {
+      const uint32_t t = tabs[w][tb][kUS * (g * kUG + s) + seg];
+      const uint32_t o = ((CHK && !EXACT) ? t & ~3u : t) + lane16;
+      al[slot][s] = EXACT ? 0u : t & 3u;
+      if (V == 0 || ((V == 4 || V == 5) && s == kUG - 1)) {
         ps[slot][s] = __builtin_amdgcn_raw_buffer_load_b128(ra, o, 0, 0);
         pq[slot][s] = __builtin_amdgcn_raw_buffer_load_b128(rb, o, 0, 0);
       } else {
@@ -184,8 +198,30 @@ __global__ void __launch_bounds__(kWG, 4) k_units(const char *a, const char *b, 
     }
     if (V == 3) touch(tb, g, slot);
   };
-  uint32_t x = 0;
+  uint32_t x = 0, y = 0;
   auto consume = [&](int slot) {
+    if (CHK) {
+#pragma unroll
+      for (int s = 0; s < kUG; ++s) {
+        const uint32_t P[4] = {ps[slot][s].x, ps[slot][s].y, ps[slot][s].z, ps[slot][s].w};
+        const uint32_t Q[4] = {pq[slot][s].x, pq[slot][s].y, pq[slot][s].z, pq[slot][s].w};
+        const uint32_t np = __builtin_amdgcn_mov_dpp(P[0], 0x130, 0xF, 0xF, true);   // lane + 1 (wave_shl:1)
+        const uint32_t nq = __builtin_amdgcn_mov_dpp(Q[0], 0x130, 0xF, 0xF, true);
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int nv = kL - (16 * (lane % 10) + 4 * k);   // the read's bytes left at this word
+          const uint32_t m = seg >= kUS || nv <= 0 ? 0u : nv >= 4 ? 0xFFFFFFFFu : (1u << (8 * nv)) - 1u;
+          const uint32_t sw = EXACT ? P[k] : __builtin_amdgcn_alignbyte(k < 3 ? P[(k + 1) & 3] : np, P[k], al[slot][s]);
+          const uint32_t qw = EXACT ? Q[k] : __builtin_amdgcn_alignbyte(k < 3 ? Q[(k + 1) & 3] : nq, Q[k], al[slot][s]);
+          sum = __builtin_amdgcn_sad_u8(sw & m, 0u, sum);
+          sum = __builtin_amdgcn_sad_u8(qw & m, 0u, sum);
+        }
+        x += sum * (1u + (uint32_t)(lane % 10));
+        y += sum;
+      }
+      return;
+    }
 #pragma unroll
     for (int s = 0; s < kUG; ++s)
       x ^= ps[slot][s].x ^ ps[slot][s].y ^ ps[slot][s].z ^ ps[slot][s].w ^ pq[slot][s].x ^ pq[slot][s].y ^
@@ -217,6 +253,32 @@ __global__ void __launch_bounds__(kWG, 4) k_units(const char *a, const char *b, 
     tb ^= 1;
   }
   out[blockIdx.x * kWG + threadIdx.x] = x;
+  if (CHK) out[(gridDim.x + blockIdx.x) * kWG + threadIdx.x] = y;
+}
+
+// `units check`: patterned bytes, their plain sum, and the two totals of a CHK pass
+__global__ void k_fill(char *a, char *b, uint32_t n) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    a[i] = (char)((i * 2654435761u) >> 24);
+    b[i] = (char)(((i + 12345u) * 40503u) >> 9);
+  }
+}
+__global__ void k_sum(const char *a, const char *b, uint32_t n, unsigned long long *tot) {
+  unsigned long long t = 0;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    t += (uint8_t)a[i] + (uint32_t)(uint8_t)b[i];
+  atomicAdd(tot, t);
+}
+template <int V>
+void run_check(const char *a, const char *b, uint32_t n, const int32_t *idx, int64_t nreads, uint32_t *out, int cus,
+               unsigned long long (&tot)[2]) {
+  const int grid = cus * 4;
+  std::vector<uint32_t> h((size_t)2 * grid * kWG);
+  k_units<V, true><<<grid, kWG>>>(a, b, n, idx, nreads, out, 0);
+  hipMemcpy(h.data(), out, h.size() * 4, hipMemcpyDeviceToHost);
+  tot[0] = tot[1] = 0;
+  for (size_t i = 0; i < h.size(); ++i) tot[i >= h.size() / 2] += h[i];
+  std::printf("units check V%d: weighted %llu plain %llu\n", V, tot[0], tot[1]);
 }
 
 // `stream_rates units [chain ...]`: only the unit-order kernels, one line per
@@ -258,6 +320,19 @@ int main(int argc, char **argv) {
   hipEventCreate(&e0);
   hipEventCreate(&e1);
   if (argc > 1 && std::string(argv[1]) == "units") {
+    if (argc > 2 && std::string(argv[2]) == "check") {
+      unsigned long long *tot, want = 0, t4[2], t5[2];
+      hipMalloc(&tot, 8);
+      hipMemset(tot, 0, 8);
+      k_fill<<<cus * 8, 256>>>(a, b, n + 256);
+      k_sum<<<cus * 8, 256>>>(a, b, n, tot);
+      hipMemcpy(&want, tot, 8, hipMemcpyDeviceToHost);
+      run_check<4>(a, b, n, idx, nreads, out, cus, t4);
+      run_check<5>(a, b, n, idx, nreads, out, cus, t5);
+      const bool ok = t4[0] == t5[0] && t4[1] == t5[1] && t4[1] == want;
+      std::printf("units check: all bytes %llu: %s\n", want, ok ? "EQUAL" : "DIFFERENT");
+      return ok ? 0 : 1;
+    }
     std::vector<int> chains;
     for (int i = 2; i < argc; ++i) chains.push_back(std::atoi(argv[i]));
     if (chains.empty()) chains.push_back(110);
@@ -267,6 +342,7 @@ int main(int argc, char **argv) {
       run_units<2>(a, b, n, idx, nreads, out, cus, c, e0, e1);
       run_units<3>(a, b, n, idx, nreads, out, cus, c, e0, e1);
       run_units<4>(a, b, n, idx, nreads, out, cus, c, e0, e1);
+      run_units<5>(a, b, n, idx, nreads, out, cus, c, e0, e1);
     }
     return 0;
   }
