@@ -304,29 +304,6 @@ static int scan_tmp(hpgq_parser *p, size_t need) {
 
 extern "C" {
 
-int64_t hpgq_fastq_complete_prefix(const char *buf, int64_t n, int at_eof) {
-  if (!buf || n <= 0) return 0;
-  if (at_eof) return n;
-  // from the end: the last line start '@' whose 4 lines are complete and
-  // well formed ('+' third line, quality as long as the sequence)
-  for (int64_t p = n - 1; p >= 0; --p) {
-    if (buf[p] != '@' || (p > 0 && buf[p - 1] != '\n')) continue;
-    int64_t b[4], e[4], q = p;
-    int k = 0;
-    for (; k < 4; ++k) {
-      const void *nl = std::memchr(buf + q, '\n', (size_t)(n - q));
-      if (!nl) break;
-      b[k] = q;
-      e[k] = (const char *)nl - buf;
-      q = e[k] + 1;
-    }
-    if (k < 4) continue;   // a partial record: look further back
-    auto len = [&](int j) { return (e[j] > b[j] && buf[e[j] - 1] == '\r') ? e[j] - 1 - b[j] : e[j] - b[j]; };
-    if (buf[b[2]] == '+' && len(1) == len(3)) return e[3] + 1;
-  }
-  return 0;
-}
-
 int hpgq_parser_open(hpgq_parser_t **ps, int device, void *stream) {
   if (!ps) return HPGQ_E_INVALID;
   *ps = nullptr;

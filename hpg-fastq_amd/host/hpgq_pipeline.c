@@ -5,10 +5,10 @@
  * worker threads (bioinfo-libs filter / stats / edit) and an ordered consumer
  * (merge or write), src/stats_fastq.c:174-250, src/filter_fastq.c:106-174,
  * src/edit_fastq.c:113-206.  Here:
- *   reader     fills page-locked chunks of FASTQ text (--chunk-mb), with
- *              --num-threads parallel pread()s, cut at the last whole record
- *              (hpgq_fastq_complete_prefix); the partial record is carried
- *              into the next chunk.
+ *   reader     one thread fills page-locked chunks of FASTQ text (--chunk-mb)
+ *              through hpgq_reader.c: --num-threads parallel pread()s, every
+ *              chunk cut at a record end and the rest carried into the next
+ *              one.  Single-end input is one side holding one mate.
  *   GPU        --gpu-workers threads per GPU (default 2: one copies a chunk
  *              in while the other's kernels run) on --gpus devices (default
  *              every visible one), chunk k on worker k mod G: hpgq_parse_host (H2D +
@@ -37,16 +37,15 @@
  *              are truncated to their final sizes at the end.  Otherwise
  *              (--stream-writer, or a map that fails) one writer thread
  *              writes the chunks in order.
- *   paired     (--fq1 + --fq2, or --interleaved -f) the reader
- *              fills a second page-locked text per chunk, counts each pread
- *              piece's lines in its pread worker and cuts both texts at the
- *              same record count (an interleaved text at an even one), each
- *              side with its own carry; the worker parses both mates (or
- *              splits the interleaved text on the device), checks the mate
- *              names (hpgq_parse_pair_check) and makes one engine call over
- *              the pairs; the stream writer writes passed_1/_2, failed_1/_2
- *              (edit_1/_2).  A pair out of step ends the run with its number
- *              over the whole input.
+ *   paired     (--fq1 + --fq2, or --interleaved -f) two mates
+ *              on two sides or on one: the reader fills a second page-locked
+ *              text per chunk for --fq2 and cuts both texts at the same record
+ *              count (an interleaved text at an even one); the worker parses
+ *              both mates (or splits the interleaved text on the device),
+ *              checks the mate names (hpgq_parse_pair_check) and makes one
+ *              engine call over the pairs; the stream writer writes
+ *              passed_1/_2, failed_1/_2 (edit_1/_2).  A pair out of step ends
+ *              the run with its number over the whole input.
  * Stats never leave the device until the end (hpgq_read_counters).
  */
 #define _GNU_SOURCE
@@ -66,16 +65,17 @@
 
 #include "hpgq_cli.h"
 #include "hpgq_mapout.h"
+#include "hpgq_reader.h"
 
 #define MAX_WORKERS 16
 #define MAX_SLOTS (2 * MAX_WORKERS + 2)
-#define MAX_CARRY (64u << 20)   /* longest record the reader can carry over */
+#define MAX_CARRY (64u << 20)    /* longest record the reader can carry over */
+#define SPLIT_MIN (4u << 20)     /* a read below this is one pread, not --num-threads */
 #define TRACE_MAX 1024
 
 typedef struct {
   char *buf;          /* page-locked */
-  size_t cap, len, use;
-  int eof;
+  size_t cap, use;
   int state;          /* 0 free, 1 filled (reader -> GPU), 2 processed (GPU -> writer) */
   int64_t chunk;      /* the chunk it holds */
   /* GPU results for the writer */
@@ -89,7 +89,7 @@ typedef struct {
    * mates (mate_view): trim and idx one mate after the other, the record
    * offsets per text */
   char *buf2;
-  size_t len2, use2;
+  size_t use2;
   int64_t pair0;
   /* edit: the chunk's output records per mate and class ([2 m + c]; c: 0
    * edit.fq / passed, 1 failed), assembled by the GPU worker so the writer only
@@ -103,35 +103,21 @@ typedef struct {
   int parts_left;
 } slot_t;
 
-/* paired input: one side of the reader (--fq1, --fq2; or the interleaved file) */
-typedef struct {
-  int fd;
-  off_t size, pos;
-  char *carry;
-  size_t carry_len;
-  int64_t carry_lines;   /* '\n' bytes in the carry */
-  const char *name;
-} side_t;
-
 typedef struct {
   const cli_options_t *o;
-  int fd;
-  off_t size, pos;
+  reader_t *rd;
   int nslots, nworkers;
   slot_t slot[MAX_SLOTS];
-  char *carry;
-  size_t carry_len;
   pthread_mutex_t mu;
   pthread_cond_t cv;
   int reader_done, error;
   int64_t chunks;
-  FILE *out_pass, *out_fail;
-  uint64_t written_pass, written_fail;
-  /* paired input: the sides, mate 2's outputs ([0] passed_2 / edit_2, [1]
-   * failed_2; out_pass / out_fail are mate 1's) and the first pair out of step */
+  /* the mates (2: paired input) and the texts per chunk they come in (2:
+   * --fq2); the output files per mate and class ([2 m + c] like slot_t.out:
+   * passed / edit, failed; NULL: not written) and the first pair out of step */
   int nmates, nsides;
-  side_t side[2];
-  FILE *out2[2];
+  FILE *out[4];
+  uint64_t written_pass, written_fail;
   int64_t bad_pair, bad_chunk;
   char pairing_msg[512];
   /* mapped outputs: [0] passed / edit.fq, [1] failed.fq (NULL: not written) */
@@ -149,7 +135,6 @@ typedef struct {
   pthread_cond_t cq_cv;
   int copies_pending;    /* slots in state 3 (under mu) */
   pthread_t copier[64];
-  int64_t cg_batch;   /* --cg: bytes of FASTQ text per chaos-game call (0: off) */
   /* HPGQ_TRACE=1: per chunk (the first TRACE_MAX) the reader's and the worker's
    * start / end times, printed to stderr at the end (diagnostics only) */
   int trace;
@@ -215,178 +200,12 @@ static void bind_numa(const cli_options_t *o, int ngpus, int ndev) {
 
 /* ---- reader ------------------------------------------------------------- */
 
-typedef struct {
-  int fd;
-  char *dst;
-  size_t n;
-  off_t off;
-  ssize_t got;
-  int count;        /* paired reader: count the piece's lines here, in parallel */
-  int64_t lines;
-} pread_job_t;
-
-static void *pread_worker(void *arg) {
-  pread_job_t *j = arg;
-  size_t done = 0;
-  while (done < j->n) {
-    ssize_t r = pread(j->fd, j->dst + done, j->n - done, j->off + (off_t)done);
-    if (r < 0 && errno == EINTR) continue;
-    if (r < 0) {
-      j->got = -1;
-      return NULL;
-    }
-    if (r == 0) break;
-    done += (size_t)r;
-  }
-  j->got = (ssize_t)done;
-  if (j->count) j->lines = hpgq_fastq_count_lines(j->dst, (int64_t)done);
-  return NULL;
-}
-
-/* a piece of a side's buffer and the lines that end in it */
-typedef struct {
-  size_t off, len;
-  int64_t lines;
-} piece_t;
-#define MAX_PIECES 66
-
-/* read up to n bytes of fd at pos with the reader threads; pc (paired reader):
- * the pieces read, appended at pc[*npc], each with its line count */
-static ssize_t read_parallel_fd(pipe_t *P, int fd, off_t pos, char *dst, size_t n, const char *base, piece_t *pc,
-                                int *npc) {
-  const int nt = P->o->num_threads;
-  if (nt <= 1 || n < (4u << 20)) {
-    pread_job_t j = {fd, dst, n, pos, 0, pc != NULL, 0};
-    pread_worker(&j);
-    if (pc && j.got > 0) pc[(*npc)++] = (piece_t){(size_t)(dst - base), (size_t)j.got, j.lines};
-    return j.got;
-  }
-  pthread_t th[64];
-  pread_job_t jobs[64];
-  const int k = nt > 64 ? 64 : nt;
-  const size_t per = (n + k - 1) / k;
-  int started = 0;
-  for (int i = 0; i < k; ++i) {
-    const size_t a = (size_t)i * per;
-    if (a >= n) break;
-    jobs[i] = (pread_job_t){fd, dst + a, (a + per > n ? n - a : per), pos + (off_t)a, 0, pc != NULL, 0};
-    pthread_create(&th[i], NULL, pread_worker, &jobs[i]);
-    started++;
-  }
-  ssize_t total = 0;
-  int short_read = 0, failed = 0;
-  for (int i = 0; i < started; ++i) {
-    pthread_join(th[i], NULL);
-    if (jobs[i].got < 0) failed = 1;
-    if (!short_read && jobs[i].got > 0) {
-      total += jobs[i].got;
-      if (pc) pc[(*npc)++] = (piece_t){(size_t)(jobs[i].dst - base), (size_t)jobs[i].got, jobs[i].lines};
-    }
-    if (jobs[i].got < 0 || (size_t)jobs[i].got < jobs[i].n) short_read = 1;   /* EOF inside this piece */
-  }
-  return failed ? -1 : total;
-}
-
-/* read up to n bytes at P->pos with the reader threads */
-static ssize_t read_parallel(pipe_t *P, char *dst, size_t n) {
-  return read_parallel_fd(P, P->fd, P->pos, dst, n, dst, NULL, NULL);
-}
-
 static void reader_fail(pipe_t *P, int code) {
   pthread_mutex_lock(&P->mu);
   P->error = code;
   pthread_cond_broadcast(&P->cv);
   pthread_mutex_unlock(&P->mu);
 }
-
-static void *reader_main(void *arg) {
-  pipe_t *P = arg;
-  int64_t target = 0;   /* --cg: file offset of the current chaos-game batch end */
-  for (int64_t k = 0;; ++k) {
-    slot_t *s = &P->slot[k % P->nslots];
-    pthread_mutex_lock(&P->mu);
-    while (s->state != 0 && !P->error) pthread_cond_wait(&P->cv, &P->mu);
-    const int err = P->error;
-    pthread_mutex_unlock(&P->mu);
-    if (err) break;
-    trace_at(P, k, 0, -1);
-    memcpy(s->buf, P->carry, P->carry_len);
-    s->len = P->carry_len;
-    const off_t g0 = P->pos - (off_t)P->carry_len;   /* file offset of buf[0] */
-    int64_t use = 0;
-    if (P->cg_batch > 0) {
-      /* the next batch end(s): the last record ending at or before target */
-      for (;;) {
-        target += P->cg_batch;
-        const size_t want = (size_t)(target - g0) < s->cap - 1 ? (size_t)(target - g0) : s->cap - 1;
-        if (want > s->len) {
-          const ssize_t got = read_parallel(P, s->buf + s->len, want - s->len);
-          if (got < 0) {
-            use = -1;   /* an I/O error, reported as such below */
-            break;
-          }
-          P->pos += got;
-          s->len += (size_t)got;
-        }
-        s->eof = P->pos >= P->size;
-        if (s->eof) break;
-        use = hpgq_fastq_complete_prefix(s->buf, (int64_t)s->len, 0);
-        if (use > 0 || s->len >= s->cap - 1) break;
-        /* no record ends in this batch (one longer than the batch): the next */
-      }
-    } else {
-      const size_t room = s->cap - 1 - s->len;   /* 1 byte for a final newline */
-      const ssize_t got = read_parallel(P, s->buf + s->len, room);
-      if (got < 0) {
-        reader_fail(P, HPGQ_E_IO);
-        break;
-      }
-      P->pos += got;
-      s->len += (size_t)got;
-      s->eof = P->pos >= P->size;
-    }
-    if (use < 0) {
-      reader_fail(P, HPGQ_E_IO);
-      break;
-    }
-    if (s->eof && s->len > 0 && s->buf[s->len - 1] != '\n') s->buf[s->len++] = '\n';
-    if (s->eof || P->cg_batch <= 0) use = hpgq_fastq_complete_prefix(s->buf, (int64_t)s->len, s->eof);
-    if (use <= 0 && !s->eof) {
-      fprintf(stderr, "hpg-fastq: a record longer than --chunk-mb, or not FASTQ\n");
-      pthread_mutex_lock(&P->mu);
-      P->error = HPGQ_E_FORMAT;
-      pthread_cond_broadcast(&P->cv);
-      pthread_mutex_unlock(&P->mu);
-      break;
-    }
-    s->use = (size_t)(use > 0 ? use : 0);
-    P->carry_len = s->len - s->use;
-    if (P->carry_len > MAX_CARRY) {
-      pthread_mutex_lock(&P->mu);
-      P->error = HPGQ_E_FORMAT;
-      pthread_cond_broadcast(&P->cv);
-      pthread_mutex_unlock(&P->mu);
-      break;
-    }
-    memcpy(P->carry, s->buf + s->use, P->carry_len);
-    trace_at(P, k, 1, -1);
-    pthread_mutex_lock(&P->mu);
-    s->chunk = k;
-    s->state = 1;
-    P->chunks = k + 1;
-    if (s->eof) P->reader_done = 1;
-    pthread_cond_broadcast(&P->cv);
-    pthread_mutex_unlock(&P->mu);
-    if (s->eof) break;
-  }
-  pthread_mutex_lock(&P->mu);
-  P->reader_done = 1;
-  pthread_cond_broadcast(&P->cv);
-  pthread_mutex_unlock(&P->mu);
-  return NULL;
-}
-
-/* ---- paired reader ------------------------------------------------------- */
 
 /* A pairing error: keeps the lowest pair number reported, so
  * that workers on different chunks agree on the first bad pair. */
@@ -402,80 +221,11 @@ static void pairing_fail(pipe_t *P, int64_t chunk, int64_t pair, const char *msg
   pthread_mutex_unlock(&P->mu);
 }
 
-/* The carry and a read of this side into buf: about `chunk` bytes in all, so
- * the side with the shorter records, which carries more of them over every cut,
- * reads less the next time and its carry does not grow.  pc: the pieces (the
- * carry first), each with its line count from the pread workers. */
-static int fill_side(pipe_t *P, side_t *sd, char *buf, size_t cap, size_t chunk, size_t *len, piece_t *pc,
-                     int *npc) {
-  *npc = 0;
-  memcpy(buf, sd->carry, sd->carry_len);
-  if (sd->carry_len) pc[(*npc)++] = (piece_t){0, sd->carry_len, sd->carry_lines};
-  *len = sd->carry_len;
-  size_t want = sd->carry_len < chunk ? chunk - sd->carry_len : 0;
-  if (want > cap - 1 - *len) want = cap - 1 - *len;   /* 1 byte for a final newline */
-  if (want > 0 && sd->pos < sd->size) {
-    const ssize_t got = read_parallel_fd(P, sd->fd, sd->pos, buf + *len, want, buf, pc, npc);
-    if (got < 0) return HPGQ_E_IO;
-    sd->pos += got;
-    *len += (size_t)got;
-    if (got == 0) sd->size = sd->pos;   /* (the file shrank: its end is here) */
-  }
-  if (sd->pos >= sd->size && *len > 0 && buf[*len - 1] != '\n') {   /* the last line lacks its newline */
-    buf[(*len)++] = '\n';
-    pc[(*npc)++] = (piece_t){*len - 1, 1, 1};
-  }
-  return 0;
-}
-
-/* bytes of the first n records of buf, n <= the whole records in it: the pieces'
- * line counts lead to the last piece that starts before record n's end, and
- * hpgq_fastq_record_prefix counts on from the record start that follows it */
-static size_t cut_records(const char *buf, size_t len, const piece_t *pc, int npc, int64_t n) {
-  size_t anchor = 0;
-  int64_t before = 0, lines = 0;   /* whole records before the anchor; lines before piece p */
-  for (int p = 1; p < npc; ++p) {
-    lines += pc[p - 1].lines;
-    if ((lines + 3) / 4 >= n) break;
-    /* piece p starts inside line `lines`: (4 - lines % 4) % 4 newlines on, record ceil(lines / 4)
-     * starts; with lines % 4 == 0 the piece starts inside that record's first line, which counts
-     * the same for hpgq_fastq_record_prefix (it looks at newlines only) */
-    size_t a = pc[p].off;
-    for (int k = (int)((4 - lines % 4) % 4); k > 0 && a < len; --k) {
-      const char *nl = memchr(buf + a, '\n', len - a);
-      a = nl ? (size_t)(nl - buf) + 1 : len;
-    }
-    anchor = a;
-    before = (lines + 3) / 4;
-  }
-  int64_t got = 0;
-  return anchor + (size_t)hpgq_fastq_record_prefix(buf + anchor, (int64_t)(len - anchor), n - before, &got);
-}
-
-static int blank_only(const char *p, size_t n) {
-  for (size_t i = 0; i < n; ++i)
-    if (p[i] != '\n' && p[i] != '\r') return 0;
-  return 1;
-}
-
-static int64_t piece_lines(const piece_t *pc, int npc) {
-  int64_t t = 0;
-  for (int p = 0; p < npc; ++p) t += pc[p].lines;
-  return t;
-}
-
-/* The reader for paired input.  Two files: a chunk of each, each with its own
- * carry, both cut at n = min(whole records in either); the rest of each side is
- * carried.  --interleaved: one file, cut at an even record count.  At the end
- * every side must be at EOF with nothing carried; otherwise the pairing error
- * names the file that has records left.  pair0 of a chunk is the whole-input
- * number of its first pair. */
-static void *reader_paired_main(void *arg) {
+/* Chunk k into slot k mod nslots once it is free.  An error at the end of the
+ * input is raised after the last chunk is published: its pairs go to a worker,
+ * whose name check may find an earlier bad pair. */
+static void *reader_main(void *arg) {
   pipe_t *P = arg;
-  const int ns = P->nsides;
-  const size_t chunk = (size_t)P->o->chunk_mb << 20;
-  int64_t pairs = 0;
-  char msg[512];
   for (int64_t k = 0;; ++k) {
     slot_t *s = &P->slot[k % P->nslots];
     pthread_mutex_lock(&P->mu);
@@ -484,74 +234,27 @@ static void *reader_paired_main(void *arg) {
     pthread_mutex_unlock(&P->mu);
     if (err) break;
     trace_at(P, k, 0, -1);
-    char *buf[2] = {s->buf, s->buf2};
-    size_t len[2] = {0, 0}, use[2] = {0, 0};
-    piece_t pc[2][MAX_PIECES];
-    int npc[2] = {0, 0}, eof[2] = {1, 1}, rc = 0;
-    int64_t lines[2] = {0, 0}, rec[2] = {0, 0};
-    for (int m = 0; m < ns && rc == 0; ++m) {
-      rc = fill_side(P, &P->side[m], buf[m], s->cap, chunk, &len[m], pc[m], &npc[m]);
-      eof[m] = P->side[m].pos >= P->side[m].size;
-      lines[m] = piece_lines(pc[m], npc[m]);
-      rec[m] = lines[m] / 4;
-    }
+    char *const buf[2] = {s->buf, s->buf2};
+    reader_chunk_t c;
+    const int rc = reader_next(P->rd, buf, s->cap, &c);
     if (rc) {
       reader_fail(P, rc);
       break;
     }
-    /* records per side in this chunk */
-    int64_t n = ns == 2 ? (rec[0] < rec[1] ? rec[0] : rec[1]) : rec[0] & ~(int64_t)1;
-    const int any_eof = eof[0] || (ns == 2 && eof[1]);
-    const int last = (eof[0] && eof[1]) || (n == 0 && any_eof);
-    if (n == 0 && !last) {
-      fprintf(stderr, "hpg-fastq: a record longer than --chunk-mb, or not FASTQ\n");
-      reader_fail(P, HPGQ_E_FORMAT);
-      break;
-    }
-    for (int m = 0; m < ns; ++m) {
-      side_t *sd = &P->side[m];
-      use[m] = n > 0 ? cut_records(buf[m], len[m], pc[m], npc[m], n) : 0;
-      sd->carry_len = len[m] - use[m];
-      sd->carry_lines = lines[m] - 4 * n;
-      memcpy(sd->carry, buf[m] + use[m], sd->carry_len);
-    }
-    /* at the end nothing may be left on either side (blank lines aside); the
-     * error is raised after the chunk's own pairs have gone to a worker, whose
-     * name check may find an earlier bad pair */
-    int tail_err = 0;
-    const int64_t npairs = pairs + (ns == 2 ? n : n / 2);
-    for (int m = 0; last && m < ns && !tail_err; ++m) {
-      const side_t *sd = &P->side[m];
-      if (sd->pos >= sd->size && blank_only(sd->carry, sd->carry_len)) continue;
-      if (rec[m] > n || sd->pos < sd->size) {   /* whole records without a mate */
-        if (ns == 2)
-          snprintf(msg, sizeof(msg), "pair %lld: %s has records left after the last record of %s",
-                   (long long)npairs, sd->name, P->side[1 - m].name);
-        else
-          snprintf(msg, sizeof(msg), "pair %lld: %s holds an odd number of records", (long long)npairs, sd->name);
-        tail_err = HPGQ_E_PAIRING;
-      } else {   /* a partial record at the end of the file */
-        tail_err = HPGQ_E_FORMAT;
-      }
-    }
-    s->len = len[0];
-    s->use = use[0];
-    s->len2 = len[1];
-    s->use2 = use[1];
-    s->eof = last;
-    s->pair0 = pairs;
-    pairs += ns == 2 ? n : n / 2;
+    s->use = c.use[0];
+    s->use2 = c.use[1];
+    s->pair0 = c.pair0;
     trace_at(P, k, 1, -1);
     pthread_mutex_lock(&P->mu);
     s->chunk = k;
     s->state = 1;
     P->chunks = k + 1;
-    if (last) P->reader_done = 1;
+    if (c.last) P->reader_done = 1;
     pthread_cond_broadcast(&P->cv);
     pthread_mutex_unlock(&P->mu);
-    if (tail_err == HPGQ_E_PAIRING) pairing_fail(P, k + 1, npairs, msg);
-    else if (tail_err) reader_fail(P, tail_err);
-    if (last) break;
+    if (c.tail_err == HPGQ_E_PAIRING) pairing_fail(P, k + 1, c.tail_pair, c.tail_msg);
+    else if (c.tail_err) reader_fail(P, c.tail_err);
+    if (c.last) break;
   }
   pthread_mutex_lock(&P->mu);
   P->reader_done = 1;
@@ -579,11 +282,10 @@ typedef struct {
 static mate_view_t mate_view(const pipe_t *P, const slot_t *s, int m) {
   const int64_t n = s->nreads;
   mate_view_t v = {s->buf, s->use, s->rec_start, s->seq_start, s->plus_start, s->qual_start, s->trim, s->idx,
-                   n, 0, 1, {P->out_pass, P->out_fail}};
+                   n, 0, 1, {P->out[2 * m], P->out[2 * m + 1]}};
   if (P->nmates == 2) {
     v.trim = s->trim + (size_t)m * n;
     v.idx = s->idx + (size_t)m * (n + 1);
-    if (m) v.f[0] = P->out2[0], v.f[1] = P->out2[1];
     if (P->nsides == 1) {   /* interleaved: records 2 i + m of the one text */
       v.total = 2 * n;
       v.first = m;
@@ -1019,9 +721,9 @@ static int place_and_copy(pipe_t *P, slot_t *s, int *handed) {
 /* map the outputs for the parallel writer (hpgq_mapout.h): each is at most
  * the input (+ the final newline the reader may add); 0 when mapped, 1: the
  * stream writer runs (files left empty), < 0 an error */
-static int map_outputs(pipe_t *P) {
-  const int fd[2] = {P->out_pass ? fileno(P->out_pass) : -1, P->out_fail ? fileno(P->out_fail) : -1};
-  P->map_cap = (size_t)P->size + 4096;
+static int map_outputs(pipe_t *P, off_t input_size) {
+  const int fd[2] = {P->out[0] ? fileno(P->out[0]) : -1, P->out[1] ? fileno(P->out[1]) : -1};
+  P->map_cap = (size_t)input_size + 4096;
   /* --prefault-threads N: populate two chunks ahead of the placed records on
    * N threads.  Default none past the reserved first window: on MI355X boxes
    * the prefault threads made stored `filter` slower (same box, alternating:
@@ -1051,8 +753,7 @@ typedef struct {
   const hpgq_params_t *p;
   int w, device;
   hpgq_ctx_t *ctx;
-  hpgq_parser_t *ps;
-  hpgq_parser_t *ps2;   /* --fq2: mate 2's parser, on the ctx stream too */
+  hpgq_parser_t *ps[2];   /* one per side ([1]: --fq2), both on the ctx stream */
   hpgq_kmers_t *km;
   hpgq_cgr_t *cg;
   uint8_t *d_mask;
@@ -1068,8 +769,7 @@ typedef struct {
 static int worker_open(worker_t *W) {
   const cli_options_t *o = W->P->o;
   int rc = hpgq_open(&W->ctx, W->device, W->p);
-  if (rc == 0) rc = hpgq_parser_open(&W->ps, W->device, hpgq_stream(W->ctx));
-  if (rc == 0 && W->P->nsides == 2) rc = hpgq_parser_open(&W->ps2, W->device, hpgq_stream(W->ctx));
+  for (int m = 0; m < W->P->nsides && rc == 0; ++m) rc = hpgq_parser_open(&W->ps[m], W->device, hpgq_stream(W->ctx));
   /* --kmers counts the reads the stats merge (passed ones when filtering,
    * src/stats_fastq.c:268-272,384-410) on the engine's stream, after it */
   if (rc == 0 && o->kmers_on) rc = hpgq_kmers_open(&W->km, W->device, W->p->lmax, hpgq_stream(W->ctx));
@@ -1083,64 +783,11 @@ static int worker_open(worker_t *W) {
 static void worker_close(worker_t *W) {
   hpgq_device_free(W->d_mask);
   hpgq_device_free(W->d_trim);
-  hpgq_parser_close(W->ps);
-  hpgq_parser_close(W->ps2);
+  hpgq_parser_close(W->ps[0]);
+  hpgq_parser_close(W->ps[1]);
   hpgq_kmers_close(W->km);
   hpgq_cgr_close(W->cg);
   hpgq_close(W->ctx);
-}
-
-/* one chunk on the worker's GPU (parse, engine, k-mers, CGR; results for the writer) */
-static int worker_chunk(worker_t *W, slot_t *s) {
-  const cli_options_t *o = W->P->o;
-  const int writes = o->command != CMD_STATS;
-  const int edit = o->command == CMD_EDIT;
-  const int need_mask = writes || ((W->km || W->cg) && o->filter_on);
-  hpgq_batch_t b;
-  int rc = hpgq_parse_host(W->ps, s->buf, (int64_t)s->use, &b);
-  trace_at(W->P, s->chunk, 5, -1);
-  if (rc || b.num_reads == 0) {
-    s->nreads = 0;
-    return rc;
-  }
-  if (need_mask && (size_t)b.num_reads > W->dcap) {
-    hpgq_device_free(W->d_mask);
-    hpgq_device_free(W->d_trim);
-    W->d_mask = NULL;
-    W->d_trim = NULL;
-    W->dcap = (size_t)b.num_reads + (size_t)b.num_reads / 4 + 1024;
-    rc = hpgq_device_alloc(W->device, (void **)&W->d_mask, W->dcap);
-    if (rc == 0) rc = hpgq_device_alloc(W->device, (void **)&W->d_trim, W->dcap * 4);
-  }
-  if (rc == 0) {   /* the long-read tails for the unit's longest record: no second pass */
-    const int64_t ml = hpgq_parser_max_length(W->ps);
-    rc = hpgq_reserve_length(W->ctx, ml);
-    if (rc == 0 && W->km) rc = hpgq_kmers_reserve_length(W->km, ml);
-  }
-  if (rc == 0) rc = hpgq_run_device(W->ctx, &b, NULL, need_mask ? W->d_mask : NULL, edit ? W->d_trim : NULL);
-  if (rc == 0 && W->km) rc = hpgq_kmers_count_device(W->km, &b, o->filter_on ? W->d_mask : NULL);
-  if (rc == 0 && writes) {
-    s->nreads = b.num_reads;
-    if (ensure_results(s, b.num_reads, 1)) rc = HPGQ_E_NOMEM;
-    if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->mask, W->d_mask, (size_t)b.num_reads);
-    if (rc == 0 && edit) {
-      rc = hpgq_copy_to_host(W->ctx, s->trim, W->d_trim, (size_t)b.num_reads * 4);
-      if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->idx, b.data_indices, ((size_t)b.num_reads + 1) * 4);
-    }
-    if (rc == 0) rc = hpgq_parse_records(W->ps, s->rec_start, s->seq_start, s->plus_start, s->qual_start);
-  }
-  trace_at(W->P, s->chunk, 3, -1);
-  if (rc == 0) rc = hpgq_sync(W->ctx);
-  trace_at(W->P, s->chunk, 6, -1);
-  if (rc == 0 && edit && !W->P->mmap_out) rc = assemble_edit(W->P, s);
-  if (rc == 0 && W->cg) {   /* after the parse and the mask; settled before the next parse reuses b */
-    rc = hpgq_cgr_fill_device(W->cg, &b, o->filter_on ? W->d_mask : NULL,
-                              o->filter_on ? HPGQ_CGR_ONLY_VALID_READS : HPGQ_CGR_ALL_READS);
-    if (rc == 0) rc = hpgq_cgr_sync(W->cg);
-    if (rc == 0) W->cg_exact_calls += hpgq_cgr_last_exact(W->cg);
-  }
-  W->num_reads += (uint64_t)b.num_reads;
-  return rc;
 }
 
 /* the mate name of record r of a text, for the error line */
@@ -1154,72 +801,89 @@ static void record_name(const char *buf, size_t use, int64_t r, char *out, size_
   out[k] = 0;
 }
 
-/* one chunk of paired input: both mates parsed (two texts, or one interleaved
- * text split on the device), the mate names checked, one engine call over the
- * pairs; for filter / edit the mask, both mates' trims, data_indices and record
- * offsets come back */
-static int worker_chunk_paired(worker_t *W, slot_t *s) {
+/* One chunk on the worker's GPU: its nm mates parsed (one text, two texts, or
+ * one interleaved text split on the device), for pairs the mate names checked,
+ * one engine call, k-mers and CGR (single-end only: validation); for filter /
+ * edit the mask per read and every mate's trims and data_indices come back,
+ * and every side's record offsets. */
+static int worker_chunk(worker_t *W, slot_t *s) {
   pipe_t *P = W->P;
   const cli_options_t *o = P->o;
+  const int nm = P->nmates, ns = P->nsides;
   const int writes = o->command != CMD_STATS;
   const int edit = o->command == CMD_EDIT;
-  const int two = P->nsides == 2;
-  hpgq_batch_t b1, b2;
+  const int need_mask = writes || ((W->km || W->cg) && o->filter_on);
+  const char *const text[2] = {s->buf, s->buf2};
+  const size_t use[2] = {s->use, s->use2};
+  hpgq_batch_t b[2];
   s->nreads = 0;
-  int rc = two ? hpgq_parse_host(W->ps, s->buf, (int64_t)s->use, &b1)
-               : hpgq_parse_host_interleaved(W->ps, s->buf, (int64_t)s->use, &b1, &b2);
-  if (rc == 0 && two) rc = hpgq_parse_host(W->ps2, s->buf2, (int64_t)s->use2, &b2);
+  int rc = 0;
+  if (nm > ns) rc = hpgq_parse_host_interleaved(W->ps[0], text[0], (int64_t)use[0], &b[0], &b[1]);
+  else
+    for (int m = 0; m < ns && rc == 0; ++m) rc = hpgq_parse_host(W->ps[m], text[m], (int64_t)use[m], &b[m]);
   trace_at(P, s->chunk, 5, -1);
-  int64_t bad = -1;
-  if (rc == 0) rc = hpgq_parse_pair_check(W->ps, W->ps2, &bad);
-  if (rc == HPGQ_E_PAIRING) {
-    char msg[512], n1[160] = "", n2[160] = "";
-    if (bad >= 0 && bad < b1.num_reads && bad < b2.num_reads) {
-      record_name(s->buf, s->use, two ? bad : 2 * bad, n1, sizeof(n1));
-      record_name(two ? s->buf2 : s->buf, two ? s->use2 : s->use, two ? bad : 2 * bad + 1, n2, sizeof(n2));
-      snprintf(msg, sizeof(msg), "pair %lld: mate names differ: '%s' and '%s'", (long long)(s->pair0 + bad), n1, n2);
-    } else {
-      snprintf(msg, sizeof(msg), "pair %lld: the mates' record counts differ", (long long)(s->pair0 + (bad > 0 ? bad : 0)));
+  if (nm == 2) {
+    const int two = ns == 2;
+    int64_t bad = -1;
+    if (rc == 0) rc = hpgq_parse_pair_check(W->ps[0], W->ps[1], &bad);
+    if (rc == HPGQ_E_PAIRING) {
+      char msg[512], n1[160] = "", n2[160] = "";
+      if (bad >= 0 && bad < b[0].num_reads && bad < b[1].num_reads) {
+        record_name(s->buf, s->use, two ? bad : 2 * bad, n1, sizeof(n1));
+        record_name(two ? s->buf2 : s->buf, two ? s->use2 : s->use, two ? bad : 2 * bad + 1, n2, sizeof(n2));
+        snprintf(msg, sizeof(msg), "pair %lld: mate names differ: '%s' and '%s'", (long long)(s->pair0 + bad), n1, n2);
+      } else {
+        snprintf(msg, sizeof(msg), "pair %lld: the mates' record counts differ", (long long)(s->pair0 + (bad > 0 ? bad : 0)));
+      }
+      pairing_fail(P, s->chunk, s->pair0 + (bad > 0 ? bad : 0), msg);
+      return rc;
     }
-    pairing_fail(P, s->chunk, s->pair0 + (bad > 0 ? bad : 0), msg);
-    return rc;
   }
-  if (rc || b1.num_reads == 0) return rc;
-  const size_t n = (size_t)b1.num_reads;
-  if (n > W->dcap) {
+  if (rc || b[0].num_reads == 0) return rc;
+  const size_t n = (size_t)b[0].num_reads;
+  if (need_mask && n > W->dcap) {
     hpgq_device_free(W->d_mask);
     hpgq_device_free(W->d_trim);
     W->d_mask = NULL;
     W->d_trim = NULL;
     W->dcap = n + n / 4 + 1024;
     rc = hpgq_device_alloc(W->device, (void **)&W->d_mask, W->dcap);
-    if (rc == 0) rc = hpgq_device_alloc(W->device, (void **)&W->d_trim, W->dcap * 8);
+    if (rc == 0) rc = hpgq_device_alloc(W->device, (void **)&W->d_trim, W->dcap * 4 * (size_t)nm);
   }
-  if (rc == 0) {   /* the long-read tail for the longest record of either mate */
-    int64_t ml = hpgq_parser_max_length(W->ps);
-    if (two && hpgq_parser_max_length(W->ps2) > ml) ml = hpgq_parser_max_length(W->ps2);
+  if (rc == 0) {   /* the long-read tails for the unit's longest record: no second pass */
+    int64_t ml = hpgq_parser_max_length(W->ps[0]);
+    if (ns == 2 && hpgq_parser_max_length(W->ps[1]) > ml) ml = hpgq_parser_max_length(W->ps[1]);
     rc = hpgq_reserve_length(W->ctx, ml);
+    if (rc == 0 && W->km) rc = hpgq_kmers_reserve_length(W->km, ml);
   }
-  if (rc == 0) rc = hpgq_run_device(W->ctx, &b1, &b2, writes ? W->d_mask : NULL, edit ? W->d_trim : NULL);
+  if (rc == 0)
+    rc = hpgq_run_device(W->ctx, &b[0], nm == 2 ? &b[1] : NULL, need_mask ? W->d_mask : NULL, edit ? W->d_trim : NULL);
+  if (rc == 0 && W->km) rc = hpgq_kmers_count_device(W->km, &b[0], o->filter_on ? W->d_mask : NULL);
   if (rc == 0 && writes) {
-    s->nreads = b1.num_reads;
-    if (ensure_results(s, b1.num_reads, 2)) rc = HPGQ_E_NOMEM;
+    s->nreads = b[0].num_reads;
+    if (ensure_results(s, b[0].num_reads, nm)) rc = HPGQ_E_NOMEM;
     if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->mask, W->d_mask, n);
-    if (rc == 0 && edit) {   /* (trim_out: mate 1 at [i], mate 2 at [n + i]) */
-      rc = hpgq_copy_to_host(W->ctx, s->trim, W->d_trim, n * 8);
-      if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->idx, b1.data_indices, (n + 1) * 4);
-      if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->idx + n + 1, b2.data_indices, (n + 1) * 4);
+    if (rc == 0 && edit) {   /* (trim_out: mate m of read i at [m n + i]) */
+      rc = hpgq_copy_to_host(W->ctx, s->trim, W->d_trim, n * 4 * (size_t)nm);
+      for (int m = 0; m < nm && rc == 0; ++m)
+        rc = hpgq_copy_to_host(W->ctx, s->idx + (size_t)m * (n + 1), b[m].data_indices, (n + 1) * 4);
     }
     /* the record offsets: an interleaved text's 2 n in text order, else mate 2's after mate 1's */
-    if (rc == 0) rc = hpgq_parse_records(W->ps, s->rec_start, s->seq_start, s->plus_start, s->qual_start);
-    if (rc == 0 && two)
-      rc = hpgq_parse_records(W->ps2, s->rec_start + n, s->seq_start + n, s->plus_start + n, s->qual_start + n);
+    for (int m = 0; m < ns && rc == 0; ++m)
+      rc = hpgq_parse_records(W->ps[m], s->rec_start + m * n, s->seq_start + m * n, s->plus_start + m * n,
+                              s->qual_start + m * n);
   }
   trace_at(P, s->chunk, 3, -1);
   if (rc == 0) rc = hpgq_sync(W->ctx);
   trace_at(P, s->chunk, 6, -1);
-  if (rc == 0 && edit) rc = assemble_edit(P, s);
-  W->num_reads += (uint64_t)b1.num_reads;
+  if (rc == 0 && edit && !P->mmap_out) rc = assemble_edit(P, s);
+  if (rc == 0 && W->cg) {   /* after the parse and the mask; settled before the next parse reuses b */
+    rc = hpgq_cgr_fill_device(W->cg, &b[0], o->filter_on ? W->d_mask : NULL,
+                              o->filter_on ? HPGQ_CGR_ONLY_VALID_READS : HPGQ_CGR_ALL_READS);
+    if (rc == 0) rc = hpgq_cgr_sync(W->cg);
+    if (rc == 0) W->cg_exact_calls += hpgq_cgr_last_exact(W->cg);
+  }
+  W->num_reads += (uint64_t)b[0].num_reads;
   return rc;
 }
 
@@ -1241,7 +905,7 @@ static void *worker_main(void *arg) {
     trace_at(P, k, 2, W->w);
     const size_t use = s->use + (P->nsides == 2 ? s->use2 : 0);   /* (s is the copiers' once place_and_copy handed it over) */
     int handed = 0;
-    int rc = P->nmates == 2 ? worker_chunk_paired(W, s) : worker_chunk(W, s);
+    int rc = worker_chunk(W, s);
     if (rc == 0 && writes && P->mmap_out) {
       rc = place_and_copy(P, s, &handed);   /* (an empty chunk is placed too: input order) */
     }
@@ -1276,6 +940,11 @@ static void add_relayout(uint64_t *dst, int ld, const uint64_t *src, int ls, int
   }
 }
 
+static void close_inputs(const reader_input_t *in) {
+  for (int m = 0; m < 2; ++m)
+    if (in[m].fd >= 0) close(in[m].fd);
+}
+
 int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   pipe_t P;
   memset(&P, 0, sizeof(P));
@@ -1283,27 +952,20 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   P.o = o;
   memset(res, 0, sizeof(*res));
   res->bad_pair = -1;
-  P.fd = open(o->in_filename, O_RDONLY);
-  if (P.fd < 0) return HPGQ_E_INVALID;
-  struct stat st;
-  fstat(P.fd, &st);
-  P.size = st.st_size;
-  /* paired input: --fq1 + --fq2 are two sides, an --interleaved file one */
+  /* the mates and the sides they come on: --fq1 + --fq2 are two sides, an
+   * --interleaved file two mates on one, single-end input one mate on one */
   P.nmates = p->paired ? 2 : 1;
   P.nsides = o->in_filename2 ? 2 : 1;
   P.bad_pair = -1;
-  P.side[1].fd = -1;
-  if (p->paired) {
-    P.side[0] = (side_t){P.fd, P.size, 0, NULL, 0, 0, o->in_filename};
-    if (o->in_filename2) {
-      const int fd2 = open(o->in_filename2, O_RDONLY);
-      if (fd2 < 0 || fstat(fd2, &st)) {
-        if (fd2 >= 0) close(fd2);
-        close(P.fd);
-        return HPGQ_E_INVALID;
-      }
-      P.side[1] = (side_t){fd2, st.st_size, 0, NULL, 0, 0, o->in_filename2};
+  reader_input_t in[2] = {{-1, 0, o->in_filename}, {-1, 0, o->in_filename2}};
+  for (int m = 0; m < P.nsides; ++m) {
+    struct stat st;
+    in[m].fd = open(in[m].name, O_RDONLY);
+    if (in[m].fd < 0 || fstat(in[m].fd, &st)) {
+      close_inputs(in);
+      return HPGQ_E_INVALID;
     }
+    in[m].size = st.st_size;
   }
   pthread_mutex_init(&P.mu, NULL);
   pthread_cond_init(&P.cv, NULL);
@@ -1314,8 +976,7 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
    * one); worker w on device (gpu + w mod ngpus) mod ndev */
   const int ndev = hpgq_device_count();
   if (ndev <= 0) {
-    close(P.fd);
-    if (P.side[1].fd >= 0) close(P.side[1].fd);
+    close_inputs(in);
     return HPGQ_E_NO_DEVICE;
   }
   const int ngpus = o->num_gpus > 0 ? o->num_gpus : ndev;
@@ -1328,7 +989,7 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   P.nslots = G + 3;
   if (P.nslots > MAX_SLOTS) P.nslots = MAX_SLOTS;
   bind_numa(o, ngpus, ndev);
-  P.cg_batch = o->cg_on ? o->cg_batch_size : 0;
+  const int64_t cg_batch = o->cg_on ? o->cg_batch_size : 0;   /* --cg: bytes of FASTQ text per chaos-game call */
   worker_t W[MAX_WORKERS];
   memset(W, 0, sizeof(W));
   int rc = 0;
@@ -1341,7 +1002,7 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   }
   /* a chunk holds --chunk-mb of text (with --cg: one chaos-game batch) */
   size_t chunk = (size_t)o->chunk_mb << 20;
-  if (P.cg_batch > 0 && (size_t)P.cg_batch > chunk) chunk = (size_t)P.cg_batch;
+  if (cg_batch > 0 && (size_t)cg_batch > chunk) chunk = (size_t)cg_batch;
   const double pinned_gb = (double)P.nslots * (double)P.nsides * (double)(chunk + MAX_CARRY) / 1e9;
   if (pinned_gb > 4.0)
     fprintf(stderr, "hpg-fastq: %d chunks of %zu MB: %.1f GB of page-locked host memory\n", P.nslots,
@@ -1351,40 +1012,28 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
     rc = hpgq_host_alloc((void **)&P.slot[i].buf, P.slot[i].cap);
     if (rc == 0 && P.nsides == 2) rc = hpgq_host_alloc((void **)&P.slot[i].buf2, P.slot[i].cap);
   }
-  P.carry = malloc(MAX_CARRY + 16);
-  /* (a paired side carries whole records the other side had no mates for yet: up to a chunk) */
-  for (int m = 0; p->paired && m < P.nsides && rc == 0; ++m)
-    if (!(P.side[m].carry = malloc(chunk + MAX_CARRY))) rc = HPGQ_E_NOMEM;
+  if (rc == 0)
+    rc = reader_open(&P.rd, in, P.nsides, P.nmates, chunk, cg_batch, o->num_threads, MAX_CARRY, SPLIT_MIN);
   const int writes = o->command != CMD_STATS;
   const int edit = o->command == CMD_EDIT;
   if (rc == 0 && writes) {
-    char path[4096];
-    /* "w+": read + write, which a shared writable mapping needs (an O_WRONLY
+    /* passed.fq (edit.fq) and failed.fq (edit: with a filter only); paired input:
+     * passed_1.fq / passed_2.fq (edit_1 / edit_2), failed_1.fq / failed_2.fq.
+     * "w+": read + write, which a shared writable mapping needs (an O_WRONLY
      * descriptor cannot be mapped) */
-    /* paired input: passed_1.fq / passed_2.fq (edit_1 / edit_2), failed_1.fq / failed_2.fq */
-    snprintf(path, sizeof(path), "%s/%s%s.fq", o->out_dirname, edit ? "edit" : "passed", p->paired ? "_1" : "");
-    P.out_pass = fopen(path, "w+");
-    if (!edit || o->filter_on) {
-      snprintf(path, sizeof(path), "%s/failed%s.fq", o->out_dirname, p->paired ? "_1" : "");
-      P.out_fail = fopen(path, "w+");
-    }
-    if (!P.out_pass || ((!edit || o->filter_on) && !P.out_fail)) rc = HPGQ_E_INVALID;
-    if (P.out_pass) setvbuf(P.out_pass, NULL, _IOFBF, 16 << 20);
-    if (P.out_fail) setvbuf(P.out_fail, NULL, _IOFBF, 16 << 20);
-    if (p->paired) {
-      snprintf(path, sizeof(path), "%s/%s_2.fq", o->out_dirname, edit ? "edit" : "passed");
-      P.out2[0] = fopen(path, "w+");
-      if (!edit || o->filter_on) {
-        snprintf(path, sizeof(path), "%s/failed_2.fq", o->out_dirname);
-        P.out2[1] = fopen(path, "w+");
-      }
-      if (!P.out2[0] || ((!edit || o->filter_on) && !P.out2[1])) rc = HPGQ_E_INVALID;
-      for (int c = 0; c < 2; ++c)
-        if (P.out2[c]) setvbuf(P.out2[c], NULL, _IOFBF, 16 << 20);
+    static const char *const suffix[3] = {"", "_1", "_2"};
+    for (int i = 0; i < 2 * P.nmates; ++i) {
+      char path[4096];
+      if (i % 2 && edit && !o->filter_on) continue;
+      snprintf(path, sizeof(path), "%s/%s%s.fq", o->out_dirname, i % 2 ? "failed" : edit ? "edit" : "passed",
+               suffix[p->paired ? 1 + i / 2 : 0]);
+      P.out[i] = fopen(path, "w+");
+      if (!P.out[i]) rc = HPGQ_E_INVALID;
+      else setvbuf(P.out[i], NULL, _IOFBF, 16 << 20);
     }
     /* (paired output goes through the stream writer: the mapped path is two-output) */
     if (rc == 0 && !o->stream_writer && !p->paired) {   /* not mappable (1): the writer thread */
-      const int m = map_outputs(&P);
+      const int m = map_outputs(&P, in[0].size);
       if (m < 0) rc = m;
     }
     res->writer = P.mmap_out ? 1 : 2;
@@ -1400,7 +1049,7 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   P.t0 = t0;
   if (P.mmap_out && (rc = start_copiers(&P))) goto done;
   pthread_t reader, writer;
-  pthread_create(&reader, NULL, p->paired ? reader_paired_main : reader_main, &P);
+  pthread_create(&reader, NULL, reader_main, &P);
   const int writer_thread = writes && !P.mmap_out;
   if (writer_thread) pthread_create(&writer, NULL, writer_main, &P);
   for (int w = 0; w < G; ++w) pthread_create(&W[w].th, NULL, worker_main, &W[w]);
@@ -1503,10 +1152,8 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
 done:
   if (P.ncopiers) stop_copiers(&P);
   if (P.mmap_out) unmap_outputs(&P, &rc);
-  if (P.out_pass) fclose(P.out_pass);
-  if (P.out_fail) fclose(P.out_fail);
-  for (int c = 0; c < 2; ++c)
-    if (P.out2[c]) fclose(P.out2[c]);
+  for (int i = 0; i < 4; ++i)
+    if (P.out[i]) fclose(P.out[i]);
   for (int i = 0; i < P.nslots; ++i) {
     hpgq_host_free(P.slot[i].buf);
     hpgq_host_free(P.slot[i].buf2);
@@ -1514,12 +1161,9 @@ done:
     free(P.slot[i].parts);
     for (int c = 0; c < 4; ++c) free(P.slot[i].out[c]);
   }
-  free(P.carry);
-  free(P.side[0].carry);
-  free(P.side[1].carry);
-  if (P.side[1].fd >= 0) close(P.side[1].fd);
+  reader_close(P.rd);
+  close_inputs(in);
   free(P.cq);
   for (int w = 0; w < G; ++w) worker_close(&W[w]);
-  close(P.fd);
   return rc;
 }

@@ -5,10 +5,13 @@ pipeline's paired refactor costs single-end input.
 Two synthetic mate files (tools/fqgen.c, --reads records each, seeds 2 and 3,
 150 bp, the same names in both) are written to --dir.
 
-  (a) single-end `stats` on mate 1's file, end to end, this tree's CLI against
-      --parent-cli (a build of the parent commit) on one box: one warm-up round,
-      then --reps alternating runs each; medians and the min-max spread.
-  (b) paired `stats` on both files: pairs/s and FASTQ GB/s next to (a)'s GB/s.
+  (a) single-end `stats` and `filter` (stored through the mapped writer) on mate
+      1's file, end to end, this tree's CLI against --parent-cli (a build of the
+      parent commit) on one box: one warm-up round, then --reps alternating runs
+      each; medians and the min-max spread.
+  (b) paired `stats` on both files and on an interleaved file of half as many
+      pairs, against --parent-cli in the same way: pairs/s and FASTQ GB/s next
+      to (a)'s GB/s.
   (c) with --trace: a rocprofv3 kernel trace (a run of its own, not timed) of a
       two-file and of an interleaved paired run over --trace-pairs pairs; the
       time of pair_check_kernel and of the de-interleaving (the two extra scans'
@@ -40,12 +43,16 @@ PARSE_KERNELS = ("nl_count_kernel", "nl_write_kernel", "record_kernel", "copy_ke
                  "pair_check_kernel", "scan", "Scan", "lookback")
 
 
-def run_stats(cli, inputs, outd, threads):
-    """One `stats` run: (seconds, GB of FASTQ, reads or pairs) from the CLI's Throughput line."""
+FILTER = ["--read-quality-range", "20,", "--read-length-range", "50,"]
+
+
+def run_cli(cli, command, inputs, outd, threads):
+    """One `stats` or `filter` run: (seconds, GB of FASTQ, reads or pairs) from the CLI's Throughput line."""
     shutil.rmtree(outd, ignore_errors=True)
     os.makedirs(outd)
-    r = subprocess.run([cli, "stats", *inputs, "-o", outd, "--gpus", "1", "--gpu", "0", "--lmax", "150",
-                        "--num-threads", str(threads)], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([cli, command, *inputs, *(FILTER if command == "filter" else []), "-o", outd, "--gpus", "1",
+                        "--gpu", "0", "--lmax", "150", "--num-threads", str(threads)],
+                       capture_output=True, text=True, timeout=600)
     m = re.search(r"Throughput: (\d+) \w+, ([0-9.]+) GB of FastQ in ([0-9.]+) s", r.stdout)
     if r.returncode or not m:
         sys.exit(f"pe_rate: {cli} {inputs} -> {r.returncode}\n{r.stdout[-400:]}\n{r.stderr[-400:]}")
@@ -58,6 +65,35 @@ def summary(runs):
     gb, n = runs[0][1], runs[0][2]
     return {"seconds_runs": s, "seconds_median": round(med, 4), "seconds_min": min(s), "seconds_max": max(s),
             "fastq_GB": gb, "records": n, "GB_per_s": round(gb / med, 3), "M_per_s": round(n / med / 1e6, 3)}
+
+
+def compare(label, command, inputs, outd, a):
+    """`command` on `inputs`, end to end: this tree's CLI and, with --parent-cli, the parent's on one box,
+    one warm-up round, then --reps alternating runs each; medians and the min-max spread.  The tree's
+    median is within the parent's spread when it is no further above the parent's median than that."""
+    clis = [("this_tree", CLI)] + ([("parent", a.parent_cli)] if a.parent_cli else [])
+    runs = {name: [] for name, _ in clis}
+    for rep in range(a.reps + 1):          # round 0: warm-up, not counted
+        for name, cli in clis:
+            t = run_cli(cli, command, inputs, outd, a.threads)
+            if rep:
+                runs[name].append(t)
+            print(label, name, rep, t[0], flush=True)
+    res = {name: summary(v) for name, v in runs.items()}
+    if a.parent_cli:
+        p, t = res["parent"], res["this_tree"]
+        res["parent_spread_s"] = round(p["seconds_max"] - p["seconds_min"], 4)
+        res["median_difference_s"] = round(t["seconds_median"] - p["seconds_median"], 4)
+        res["within_parent_spread"] = t["seconds_median"] - p["seconds_median"] <= p["seconds_max"] - p["seconds_min"]
+    return res
+
+
+def interleave(f1, f2, out, pairs):
+    """The first `pairs` records of f1 and f2, alternating, into `out`."""
+    with open(f1, "rb") as a, open(f2, "rb") as b, open(out, "wb") as o:
+        for _ in range(pairs):
+            o.writelines([a.readline(), a.readline(), a.readline(), a.readline(),
+                          b.readline(), b.readline(), b.readline(), b.readline()])
 
 
 def first_records(path, n):
@@ -113,7 +149,7 @@ def main():
     # (no GPU: the first CLI run ends with "no HIP device" and so does this tool)
     tmp = tempfile.mkdtemp(prefix="hpgq_pe_")
     tag = f"hpgq_pe_{os.getpid()}"
-    f1, f2 = (os.path.join(a.dir, f"{tag}_{m}.fq") for m in (1, 2))
+    f1, f2, fi = (os.path.join(a.dir, f"{tag}_{m}.fq") for m in (1, 2, "i"))
     outd = os.path.join(a.dir, f"{tag}_out")
     small = [os.path.join(a.dir, f"{tag}_s{m}.fq") for m in (1, 2, "i")]
     res = {"tool": "pe_rate", "reads_per_file": a.reads, "reps": a.reps, "threads": a.threads,
@@ -125,31 +161,16 @@ def main():
         for f, seed in ((f1, 2), (f2, 3)):
             subprocess.run([gen, f, str(a.reads), "150", str(seed)], check=True, timeout=600,
                            env=dict(os.environ, OMP_NUM_THREADS=str(a.threads)))
-        # (a) single-end: this tree against the parent build, alternating
-        clis = [("this_tree", CLI)] + ([("parent", a.parent_cli)] if a.parent_cli else [])
-        runs = {name: [] for name, _ in clis}
-        for rep in range(a.reps + 1):          # round 0: warm-up, not counted
-            for name, cli in clis:
-                t = run_stats(cli, ["-f", f1], outd, a.threads)
-                if rep:
-                    runs[name].append(t)
-                print("single", name, rep, t[0], flush=True)
-        res["single_end"] = {name: summary(v) for name, v in runs.items()}
-        if a.parent_cli:
-            p, t = res["single_end"]["parent"], res["single_end"]["this_tree"]
-            res["single_end"]["parent_spread_s"] = round(p["seconds_max"] - p["seconds_min"], 4)
-            res["single_end"]["median_difference_s"] = round(t["seconds_median"] - p["seconds_median"], 4)
-            res["single_end"]["within_parent_spread"] = (
-                t["seconds_median"] - p["seconds_median"] <= p["seconds_max"] - p["seconds_min"])
-        # (b) paired
-        pr = []
-        for rep in range(a.reps + 1):
-            t = run_stats(CLI, ["--fq1", f1, "--fq2", f2], outd, a.threads)
-            if rep:
-                pr.append(t)
-            print("paired", rep, t[0], flush=True)
-        res["paired"] = summary(pr)
-        res["paired"]["pairs_per_s"] = round(res["paired"]["records"] / res["paired"]["seconds_median"])
+        # (a) single-end `stats` and `filter` (the mapped writer), (b) paired `stats` from two files and
+        # from one interleaved file of half as many pairs: this tree against the parent build, alternating
+        res["single_end"] = compare("single", "stats", ["-f", f1], outd, a)
+        res["single_end_filter"] = compare("filter", "filter", ["-f", f1], outd, a)
+        res["paired"] = compare("paired", "stats", ["--fq1", f1, "--fq2", f2], outd, a)
+        interleave(f1, f2, fi, a.reads // 2)
+        res["interleaved"] = compare("interleaved", "stats", ["--interleaved", "-f", fi], outd, a)
+        for k in ("paired", "interleaved"):
+            t = res[k]["this_tree"]
+            t["pairs_per_s"] = round(t["records"] / t["seconds_median"])
         # (c) kernel trace, a run of its own
         if a.trace:
             r1, r2 = first_records(f1, a.trace_pairs), first_records(f2, a.trace_pairs)
@@ -165,7 +186,7 @@ def main():
             res["trace_interleaved"] = kernel_trace(["--interleaved", "-f", small[2]], outd,
                                                     os.path.join(tmp, "ti"), a.threads)
     finally:
-        for f in [f1, f2] + small:
+        for f in [f1, f2, fi] + small:
             if os.path.exists(f):
                 os.remove(f)
         shutil.rmtree(outd, ignore_errors=True)
