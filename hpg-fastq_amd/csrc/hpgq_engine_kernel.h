@@ -771,7 +771,8 @@ __device__ void long_merge(const EngineArgs &A, const MateBuf &b, const ReadRef 
 // round() (halves away from zero; src/stats_fastq.c:317), bin = key & 255
 // (negative keys need quality bytes >= 128: bins 128..255); fx = floor(65536
 // S / n) in two's complement (the acc_quality term, HPGQ_S_ACC_MEANQ_FX16)
-__device__ __forceinline__ void meanq_terms(uint32_t sb, uint32_t n, uint32_t &bin, uint64_t &fx) {
+// (HPGQ_HD, as the two below: tests/read_terms/ runs them on the host over every (n, sb))
+HPGQ_HD __forceinline__ void meanq_terms(uint32_t sb, uint32_t n, uint32_t &bin, uint64_t &fx) {
   const uint32_t off = (uint32_t)kQBias * n;
   if (__builtin_expect(sb >= off, 1)) {
     bin = (2 * sb + n) / (2 * n) - (uint32_t)kQBias;
@@ -781,6 +782,43 @@ __device__ __forceinline__ void meanq_terms(uint32_t sb, uint32_t n, uint32_t &b
   }
   const uint32_t q = sb / n, rem = sb - q * n;
   fx = ((uint64_t)q << 16) + (((uint32_t)rem << 16) / n) - ((uint64_t)kQBias << 16);
+}
+
+// the high 32 bits of a 32 x 32-bit product and the low 32 bits of a 24 x
+// 24-bit one: the device's instructions, in plain 64-bit arithmetic on the host
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ uint32_t mul_hi_u32(uint32_t a, uint32_t b) { return __umulhi(a, b); }
+__device__ __forceinline__ uint32_t mul_u24(uint32_t a, uint32_t b) { return __umul24(a, b); }
+#else
+HPGQ_HD inline uint32_t mul_hi_u32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * b) >> 32); }
+HPGQ_HD inline uint32_t mul_u24(uint32_t a, uint32_t b) {
+  return (uint32_t)((uint64_t)(a & 0xFFFFFFu) * (uint64_t)(b & 0xFFFFFFu));
+}
+#endif
+
+// floor(x / n) for a read length 1 <= n <= 252 from rc = ceil(2^32 / n) (the
+// kernel's rtab; n = 1 has rc = 0 and one1 = 1): q = mulhi(x, rc) is exact
+// while x * (n - 1) < 2^32 (the error of rc times x stays below one unit of
+// 1 / n), which holds for every numerator of the unit epilogue (biased
+// quality sums < 2^16, 100 x G+C, remainders << 16 < n 2^16)
+HPGQ_HD __forceinline__ uint32_t div_len(uint32_t x, uint32_t rc, uint32_t one1) {
+  return mul_hi_u32(x, rc) + mul_u24(x, one1);
+}
+
+// meanq_terms for the segmented kernels' reads (n <= 252) by div_len: one
+// multiply-high per quotient instead of a 32-bit division (round 6: ~65 VALU
+// per unit epilogue and mate)
+HPGQ_HD __forceinline__ void meanq_terms_rc(uint32_t sb, uint32_t n, uint32_t rc, uint32_t one1, uint32_t &bin,
+                                            uint64_t &fx) {
+  const uint32_t off = (uint32_t)kQBias * n;
+  const uint32_t q = div_len(sb, rc, one1), rem = sb - mul_u24(q, n);
+  if (__builtin_expect(sb >= off, 1)) {
+    bin = q + (2 * rem >= n ? 1u : 0u) - (uint32_t)kQBias;   // (2 sb + n) / (2 n) - 128
+  } else {
+    const uint32_t t = off - sb, qt = div_len(t, rc, one1), rt = t - mul_u24(qt, n);
+    bin = (256u - (qt + (2 * rt >= n ? 1u : 0u))) & 255u;
+  }
+  fx = ((uint64_t)q << 16) + div_len(rem << 16, rc, one1) - ((uint64_t)kQBias << 16);
 }
 
 // Per-position fix-ups of a workgroup's partial set in LDS, from the read

@@ -361,30 +361,8 @@ __device__ __forceinline__ uint32_t trim_word(const ColdParams &C, __amdgpu_buff
   return (uint32_t)ts | ((uint32_t)te << 16);
 }
 
-// floor(x / n) for a read length 1 <= n <= 252 from rc = ceil(2^32 / n) (the
-// kernel's rtab; n = 1 has rc = 0 and one1 = 1): q = mulhi(x, rc) is exact
-// while x * (n - 1) < 2^32 (the error of rc times x stays below one unit of
-// 1 / n), which holds for every numerator of the unit epilogue (biased
-// quality sums < 2^16, 100 x G+C, remainders << 16 < n 2^16)
-__device__ __forceinline__ uint32_t div_len(uint32_t x, uint32_t rc, uint32_t one1) {
-  return __umulhi(x, rc) + __umul24(x, one1);
-}
-
-// meanq_terms (hpgq_engine_kernel.h) for the segmented kernels' reads (n <=
-// 252) by div_len: one multiply-high per quotient instead of a 32-bit division
-// (round 6: ~65 VALU per unit epilogue and mate)
-__device__ __forceinline__ void meanq_terms_rc(uint32_t sb, uint32_t n, uint32_t rc, uint32_t one1, uint32_t &bin,
-                                               uint64_t &fx) {
-  const uint32_t off = (uint32_t)kQBias * n;
-  const uint32_t q = div_len(sb, rc, one1), rem = sb - __umul24(q, n);
-  if (__builtin_expect(sb >= off, 1)) {
-    bin = q + (2 * rem >= n ? 1u : 0u) - (uint32_t)kQBias;   // (2 sb + n) / (2 n) - 128
-  } else {
-    const uint32_t t = off - sb, qt = div_len(t, rc, one1), rt = t - __umul24(qt, n);
-    bin = (256u - (qt + (2 * rt >= n ? 1u : 0u))) & 255u;
-  }
-  fx = ((uint64_t)q << 16) + div_len(rem << 16, rc, one1) - ((uint64_t)kQBias << 16);
-}
+// (div_len and meanq_terms_rc, the unit epilogue's quotients, are beside
+// meanq_terms in hpgq_engine_kernel.h: a host harness checks all three)
 
 template <int M>
 struct MateTag {
