@@ -40,7 +40,7 @@ const char *hpgq_strerror(int code) {
     case HPGQ_E_INVALID: return "invalid argument";
     case HPGQ_E_HIP: return "HIP runtime error";
     case HPGQ_E_NOMEM: return "out of memory";
-    case HPGQ_E_READ_TOO_LONG: return "read longer than lmax";
+    case HPGQ_E_READ_TOO_LONG: return "read longer than the reserved rows";
     case HPGQ_E_NO_DEVICE: return "no HIP device";
     case HPGQ_E_RCCL: return "RCCL error";
     case HPGQ_E_STATE: return "invalid ctx state";

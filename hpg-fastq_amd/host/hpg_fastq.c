@@ -69,6 +69,15 @@ int main(int argc, char **argv) {
     if (!f || fwrite(r.kmers, sizeof(uint64_t), kn, f) != kn) rc = 1;
     if (f) fclose(f);
   }
+  if (o->quality_dist_out && r.qdist[0]) {   /* per mate: [npos u64 | hist u64 [npos][256]] */
+    FILE *f = fopen(o->quality_dist_out, "wb");
+    for (int m = 0; m < (p.paired ? 2 : 1); ++m) {
+      const uint64_t np = (uint64_t)r.qdist_npos[m];
+      const size_t qn = (size_t)HPGQ_QDIST_VALUES * (size_t)np;
+      if (!f || fwrite(&np, sizeof(uint64_t), 1, f) != 1 || fwrite(r.qdist[m], sizeof(uint64_t), qn, f) != qn) rc = 1;
+    }
+    if (f) fclose(f);
+  }
   if (o->cg_out && r.cg_seq) {   /* [table_seq | table_q | word count] u32 */
     const size_t cells = (size_t)1 << (2 * o->k_cg);
     FILE *f = fopen(o->cg_out, "wb");
@@ -83,6 +92,11 @@ int main(int argc, char **argv) {
   /* paired input: one full report set per mate, from that mate's counter set */
   for (int m = 0; cmd == CMD_STATS && p.paired && m < 2; ++m)
     if (cli_report_set(o, &p, &r, counters + (size_t)m * hpgq_counters_len(r.lmax), mate_name[m])) rc = 1;
+  /* --quality-dist: one file per mate, named as that mate's report set */
+  for (int m = 0; cmd == CMD_STATS && m < (p.paired ? 2 : 1); ++m)
+    if (r.qdist[m] &&
+        cli_report_qdist(o, &p, r.qdist[m], r.qdist_npos[m], p.paired ? mate_name[m] : cli_base_name(o->in_filename)))
+      rc = 1;
 
   if (!o->quiet) {
     printf("\n\nRESULTS\n");
@@ -128,6 +142,8 @@ int main(int argc, char **argv) {
   }
   free(r.counters);
   free(r.kmers);
+  free(r.qdist[0]);
+  free(r.qdist[1]);
   free(r.cg_seq);
   free(r.cg_q);
   cli_free(o);

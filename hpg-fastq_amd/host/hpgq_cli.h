@@ -34,6 +34,7 @@ typedef struct {
   char *quality_encoding_name;
   int quality_encoding_value;
   int kmers_on;
+  int quality_dist_on;      /* stats --quality-dist */
   /* chaos game (old/main_hpg_fastq_old.c:185-189: --cg | --chaos-game, --k, --gs-filename) */
   int cg_on, k_cg;
   char *gs_filename;
@@ -55,6 +56,7 @@ typedef struct {
   char *counters_out;       /* raw u64 counter dump (tests) */
   char *kmers_out;          /* raw u64 k-mer table dump (tests) */
   char *cg_out;             /* raw u32 chaos-game tables dump (tests) */
+  char *quality_dist_out;   /* raw [npos u64 | hist] per mate dump (tests) */
   int quiet;
   int stream_writer;        /* filter / edit: one writer thread instead of mapped outputs */
   int writer_hook;          /* tests only (--writer-test-hook): hpgq_mapout.h MAPOUT_HOOK_* */
@@ -80,6 +82,8 @@ typedef struct {
   double seconds, fastq_bytes;
   uint64_t *kmers;          /* --kmers: by_pos [HPGQ_NUM_KMERS][kmers_npos] (malloc'd) */
   int kmers_npos;
+  uint64_t *qdist[2];       /* --quality-dist: per mate hist [qdist_npos][HPGQ_QDIST_VALUES] (malloc'd) */
+  int qdist_npos[2];        /* the longest counted read of the mate */
   uint32_t *cg_seq, *cg_q;  /* --cg: table_seq / table_q [dim*dim] (malloc'd) */
   uint32_t cg_words;        /* fq_word_count */
   int cg_exact_calls;       /* chaos-game calls the exact simulation redid */
@@ -100,6 +104,9 @@ int cli_report(const cli_options_t *o, const hpgq_params_t *p, const cli_result_
  * input writes one report set per mate */
 int cli_report_set(const cli_options_t *o, const hpgq_params_t *p, const cli_result_t *res,
                    const uint64_t *counters, const char *base);
+/* --quality-dist: <base>.quality.dist.per.nt.data from one mate's table */
+int cli_report_qdist(const cli_options_t *o, const hpgq_params_t *p, const uint64_t *hist, int npos,
+                     const char *base);
 const char *cli_base_name(const char *path);
 /* the report base names of the two mates: each input's base name, or
  * <base>_1 / <base>_2 for --interleaved (out: 2 x 4096 bytes) */

@@ -755,6 +755,7 @@ typedef struct {
   hpgq_ctx_t *ctx;
   hpgq_parser_t *ps[2];   /* one per side ([1]: --fq2), both on the ctx stream */
   hpgq_kmers_t *km;
+  hpgq_qdist_t *qd[2];    /* --quality-dist: one table per mate, on the ctx stream */
   hpgq_cgr_t *cg;
   uint8_t *d_mask;
   uint32_t *d_trim;
@@ -773,6 +774,10 @@ static int worker_open(worker_t *W) {
   /* --kmers counts the reads the stats merge (passed ones when filtering,
    * src/stats_fastq.c:268-272,384-410) on the engine's stream, after it */
   if (rc == 0 && o->kmers_on) rc = hpgq_kmers_open(&W->km, W->device, W->p->lmax, hpgq_stream(W->ctx));
+  /* --quality-dist counts the same reads, per mate (passed pairs for paired
+   * input): lmax rows to start with, the window of on-chip values from phred */
+  for (int m = 0; m < W->P->nmates && rc == 0 && o->quality_dist_on; ++m)
+    rc = hpgq_qdist_open(&W->qd[m], W->device, W->p->lmax, W->p->phred, hpgq_stream(W->ctx));
   /* --cg: chaos_game_fill_tables per batch (= chunk), the base quality from
    * --quality-encoding; with a filter only the passed reads (ONLY_VALID_READS
    * with the mask as read_status, old/chaos_game.c:188) */
@@ -786,6 +791,8 @@ static void worker_close(worker_t *W) {
   hpgq_parser_close(W->ps[0]);
   hpgq_parser_close(W->ps[1]);
   hpgq_kmers_close(W->km);
+  hpgq_qdist_close(W->qd[0]);
+  hpgq_qdist_close(W->qd[1]);
   hpgq_cgr_close(W->cg);
   hpgq_close(W->ctx);
 }
@@ -812,7 +819,7 @@ static int worker_chunk(worker_t *W, slot_t *s) {
   const int nm = P->nmates, ns = P->nsides;
   const int writes = o->command != CMD_STATS;
   const int edit = o->command == CMD_EDIT;
-  const int need_mask = writes || ((W->km || W->cg) && o->filter_on);
+  const int need_mask = writes || ((W->km || W->cg || W->qd[0]) && o->filter_on);
   const char *const text[2] = {s->buf, s->buf2};
   const size_t use[2] = {s->use, s->use2};
   hpgq_batch_t b[2];
@@ -855,10 +862,13 @@ static int worker_chunk(worker_t *W, slot_t *s) {
     if (ns == 2 && hpgq_parser_max_length(W->ps[1]) > ml) ml = hpgq_parser_max_length(W->ps[1]);
     rc = hpgq_reserve_length(W->ctx, ml);
     if (rc == 0 && W->km) rc = hpgq_kmers_reserve_length(W->km, ml);
+    for (int m = 0; m < nm && rc == 0 && W->qd[m]; ++m) rc = hpgq_qdist_reserve_length(W->qd[m], ml);
   }
   if (rc == 0)
     rc = hpgq_run_device(W->ctx, &b[0], nm == 2 ? &b[1] : NULL, need_mask ? W->d_mask : NULL, edit ? W->d_trim : NULL);
   if (rc == 0 && W->km) rc = hpgq_kmers_count_device(W->km, &b[0], o->filter_on ? W->d_mask : NULL);
+  for (int m = 0; m < nm && rc == 0 && W->qd[m]; ++m)   /* (paired: the pair mask for both mates) */
+    rc = hpgq_qdist_count_device(W->qd[m], &b[m], o->filter_on ? W->d_mask : NULL);
   if (rc == 0 && writes) {
     s->nreads = b[0].num_reads;
     if (ensure_results(s, b[0].num_reads, nm)) rc = HPGQ_E_NOMEM;
@@ -1116,6 +1126,27 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
         for (int j = 0; j < pw; ++j) res->kmers[(size_t)id * KP + j] += kp[(size_t)id * pw + j];
       free(kp);
     }
+  }
+  /* --quality-dist: per mate, the workers' tables added into one of the
+   * longest worker's rows (hpgq_qdist_add) */
+  for (int m = 0; m < nm && rc == 0 && o->quality_dist_on; ++m) {
+    int32_t np = 0;
+    for (int w = 0; w < G && rc == 0; ++w) {
+      int32_t pw = 0;
+      rc = hpgq_qdist_read(W[w].qd[m], NULL, 0, &pw);
+      if (pw > np) np = pw;
+    }
+    res->qdist_npos[m] = np;
+    res->qdist[m] = rc == 0 ? calloc((size_t)HPGQ_QDIST_VALUES * np + 1, sizeof(uint64_t)) : NULL;
+    if (rc == 0 && !res->qdist[m]) rc = HPGQ_E_NOMEM;
+    uint64_t *part = rc == 0 ? calloc((size_t)HPGQ_QDIST_VALUES * np + 1, sizeof(uint64_t)) : NULL;
+    if (rc == 0 && !part) rc = HPGQ_E_NOMEM;
+    for (int w = 0; w < G && rc == 0; ++w) {
+      int32_t pw = 0;
+      rc = hpgq_qdist_read(W[w].qd[m], part, (size_t)HPGQ_QDIST_VALUES * np, &pw);
+      if (rc == 0) rc = hpgq_qdist_add(res->qdist[m], np, part, pw);
+    }
+    free(part);
   }
   if (rc == 0 && o->cg_on) {
     const size_t cells = (size_t)1 << (2 * o->k_cg);

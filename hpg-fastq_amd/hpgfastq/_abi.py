@@ -25,10 +25,12 @@ ROUTES = {"auto": ROUTE_AUTO, "single": ROUTE_CATCH_ALL, "tri": ROUTE_FIRST_TRI,
           "auto_fixed": ROUTE_AUTO | ROUTE_NO_ADAPTIVE}
 
 ERRORS = {0: "ok", -1: "invalid argument", -2: "HIP runtime error", -3: "out of memory",
-          -4: "read longer than lmax (not returned since round 6)", -5: "no HIP device", -6: "RCCL error",
+          -4: "read longer than the reserved rows", -5: "no HIP device", -6: "RCCL error",
           -7: "invalid ctx state", -8: "malformed FASTQ text", -9: "file i/o error",
           -10: "mate pairs out of step"}
 E_FORMAT, E_PAIRING = -8, -10
+E_READ_TOO_LONG = -4
+QDIST_VALUES = 256
 
 
 class HpgqError(RuntimeError):
@@ -79,6 +81,11 @@ class Summary(C.Structure):
                 ("mean_length", C.c_double), ("mean_quality_raw", C.c_double),
                 ("num_A", C.c_uint64), ("num_C", C.c_uint64), ("num_G", C.c_uint64),
                 ("num_T", C.c_uint64), ("num_N", C.c_uint64)]
+
+
+class QdistRow(C.Structure):
+    _fields_ = [("count", C.c_uint64)] + [(f, C.c_int32) for f in
+                                          ("min", "p10", "q1", "median", "q3", "p90", "max")]
 
 
 class GsInfo(C.Structure):
@@ -172,6 +179,16 @@ _SIGS = [
     ("hpgq_kmers_device", C.c_void_p, [C.c_void_p]),
     ("hpgq_kmers_reserve_length", C.c_int, [C.c_void_p, C.c_int64]),
     ("hpgq_kmers_read_ext", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]),
+    ("hpgq_qdist_open", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("hpgq_qdist_close", None, [C.c_void_p]),
+    ("hpgq_qdist_reserve_length", C.c_int, [C.c_void_p, C.c_int64]),
+    ("hpgq_qdist_count_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p]),
+    ("hpgq_qdist_sync", C.c_int, [C.c_void_p]),
+    ("hpgq_qdist_reset", C.c_int, [C.c_void_p]),
+    ("hpgq_qdist_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int32)]),
+    ("hpgq_qdist_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
+    ("hpgq_qdist_add", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    ("hpgq_qdist_quantiles", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ("hpgq_synth_length", C.c_int32, [C.POINTER(Synth), C.c_int64]),
     ("hpgq_synth_indices_host", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p]),
     ("hpgq_synth_device", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p,

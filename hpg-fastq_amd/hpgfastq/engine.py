@@ -9,8 +9,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (lib, check, Params, Batch, Summary, GsInfo, counters_len, CGR_ALL_READS, ROUTES,
-                   E_PAIRING)
+from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, counters_len, CGR_ALL_READS, ROUTES,
+                   E_PAIRING, QDIST_VALUES)
 
 # Kernel route for new Engines (tests / A/B: a key of ROUTES, or None for the
 # library's automatic chain).  Applied through hpgq_debug_set_route: the
@@ -362,6 +362,93 @@ class Kmers:
         out = np.zeros((1024, P.value), dtype=np.uint64)
         check(lib.hpgq_kmers_read_ext(self._h, _ptr(out), out.size, C.byref(P)), "hpgq_kmers_read_ext")
         return out
+
+
+class QualityDist:
+    """hpgq_qdist: `stats --quality-dist`, bases per (read position, raw quality
+    byte) of the counted reads.  `rows` positions are reserved
+    (reserve_length grows them); `base` is a speed hint: the 64 byte values from
+    it are counted on chip."""
+
+    def __init__(self, rows, base=33, device=0, stream=None):
+        self._h = None
+        h = C.c_void_p()
+        check(lib.hpgq_qdist_open(C.byref(h), device, rows, base, stream), "hpgq_qdist_open")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib.hpgq_qdist_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def count_device(self, batch, mask_ptr=None):
+        check(lib.hpgq_qdist_count_device(self._h, C.byref(batch), mask_ptr), "hpgq_qdist_count_device")
+
+    def reserve_length(self, max_len):
+        check(lib.hpgq_qdist_reserve_length(self._h, int(max_len)), "hpgq_qdist_reserve_length")
+
+    def sync(self):
+        """HpgqError -4 after a counted read longer than the rows, until reset()."""
+        check(lib.hpgq_qdist_sync(self._h), "hpgq_qdist_sync")
+
+    def reset(self):
+        check(lib.hpgq_qdist_reset(self._h), "hpgq_qdist_reset")
+
+    def set_max_workgroups(self, max_wg):
+        check(lib.hpgq_qdist_debug_set_max_workgroups(self._h, max_wg),
+              "hpgq_qdist_debug_set_max_workgroups")
+
+    def hist(self):
+        """u64 [npos, 256], npos = the longest counted read (synchronises)."""
+        P = C.c_int32(0)
+        check(lib.hpgq_qdist_read(self._h, None, 0, C.byref(P)), "hpgq_qdist_read")
+        out = np.zeros((P.value, QDIST_VALUES), dtype=np.uint64)
+        check(lib.hpgq_qdist_read(self._h, _ptr(out), out.size, C.byref(P)), "hpgq_qdist_read")
+        return out
+
+
+def _qdist_table(a):
+    a = np.ascontiguousarray(a, dtype=np.uint64)
+    if a.ndim != 2 or a.shape[1] != QDIST_VALUES:
+        raise ValueError("a quality-distribution table is (npos, 256) u64")
+    return a
+
+
+def qdist_add(dst, src):
+    """hpgq_qdist_add: dst[:len(src)] += src, in place (dst: a C-contiguous
+    (npos, 256) u64 array with at least src's rows)."""
+    if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint64 and dst.flags.c_contiguous
+            and dst.ndim == 2 and dst.shape[1] == QDIST_VALUES):
+        raise ValueError("dst must be a C-contiguous (npos, 256) u64 array")
+    src = _qdist_table(src)
+    check(lib.hpgq_qdist_add(_ptr(dst), dst.shape[0], _ptr(src), src.shape[0]), "hpgq_qdist_add")
+    return dst
+
+
+def qdist_quantiles(hist, phred):
+    """hpgq_qdist_quantiles: int64 [npos, 8] = count, min, P10, Q1, median, Q3,
+    P90, max per position (qualities: (signed char)byte - phred)."""
+    hist = _qdist_table(hist)
+    rows = (QdistRow * max(hist.shape[0], 1))()
+    check(lib.hpgq_qdist_quantiles(_ptr(hist), hist.shape[0], int(phred), rows), "hpgq_qdist_quantiles")
+    out = np.zeros((hist.shape[0], 8), dtype=np.int64)
+    for p in range(hist.shape[0]):
+        r = rows[p]
+        out[p, 1:] = (r.min, r.p10, r.q1, r.median, r.q3, r.p90, r.max)
+        out.view(np.uint64)[p, 0] = r.count   # (a count of 2^63 or more: its two's complement)
+    return out
 
 
 class Signature:

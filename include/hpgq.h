@@ -64,8 +64,9 @@ extern "C" {
 #define HPGQ_E_INVALID         (-1)   /* bad argument / parameter            */
 #define HPGQ_E_HIP             (-2)   /* HIP runtime error                    */
 #define HPGQ_E_NOMEM           (-3)   /* device or host allocation failed     */
-#define HPGQ_E_READ_TOO_LONG   (-4)   /* not returned since round 6: reads of any
-                                         length merge (kept for the ABI)        */
+#define HPGQ_E_READ_TOO_LONG   (-4)   /* hpgq_qdist_sync / _read only: a counted read
+                                         longer than the reserved rows (the engine
+                                         and k-mers merge reads of any length)  */
 #define HPGQ_E_NO_DEVICE       (-5)   /* no HIP device                        */
 #define HPGQ_E_RCCL            (-6)   /* RCCL communicator / collective error */
 #define HPGQ_E_STATE           (-7)   /* call not valid in this ctx state     */
@@ -547,6 +548,59 @@ uint64_t *hpgq_kmers_device(hpgq_kmers_t *km);
 int  hpgq_kmers_reserve_length(hpgq_kmers_t *km, int64_t max_len);
 /* every start: [HPGQ_NUM_KMERS][*npos_ext] (by_pos == NULL: size query) */
 int  hpgq_kmers_read_ext(hpgq_kmers_t *km, uint64_t *by_pos, size_t n, int32_t *npos_ext);
+
+/* ---------------------------------------------------------------------- */
+/* stats --quality-dist: bases per (read position, quality byte)            */
+/* ---------------------------------------------------------------------- */
+
+/*
+ * Build-defined (the reference reports a mean per position only; DESIGN.md
+ * §2.8).  Every base j of every counted read adds 1 to hist[j][b], b its RAW
+ * quality byte as an unsigned index: hist is [npos][HPGQ_QDIST_VALUES] u64,
+ * positions from the read's first base, no lmax cap.  The table knows nothing
+ * of phred; hpgq_qdist_quantiles reads it as qualities Q = (signed char)b -
+ * phred (quirk Q13).
+ *
+ * The table has `rows` rows.  A counted read longer than the rows has only its
+ * positions below them counted and makes hpgq_qdist_sync and hpgq_qdist_read
+ * return HPGQ_E_READ_TOO_LONG until hpgq_qdist_reset: call
+ * hpgq_qdist_reserve_length first; the parser gives the longest record
+ * (hpgq_parser_max_length).  There is no second pass and no tail.
+ */
+typedef struct hpgq_qdist hpgq_qdist_t;
+#define HPGQ_QDIST_VALUES 256
+typedef struct hpgq_qdist_row { uint64_t count; int32_t min, p10, q1, median, q3, p90, max; } hpgq_qdist_row_t;
+
+/* rows >= 1; 0 <= base <= 192: the 64 byte values [base, base + 64) are
+ * counted on chip, the others by a slower path -- a speed hint (pass phred),
+ * the table is exact for all 256 values whatever it is.  stream: as
+ * hpgq_kmers_open.  HPGQ_E_INVALID before any device call. */
+int  hpgq_qdist_open(hpgq_qdist_t **qd, int device, int rows, int base, void *stream);
+void hpgq_qdist_close(hpgq_qdist_t *qd);
+/* grow the table to >= max_len rows (counts kept; async on the stream; never shrinks) */
+int  hpgq_qdist_reserve_length(hpgq_qdist_t *qd, int64_t max_len);
+/* Count a DEVICE batch, async; only `quality` and `data_indices` are read
+ * (quality readable HPGQ_DEVICE_SLACK bytes past the data end); mask (device,
+ * may be NULL): only reads with mask[i] == 1 are counted. */
+int  hpgq_qdist_count_device(hpgq_qdist_t *qd, const hpgq_batch_t *b, const uint8_t *mask);
+int  hpgq_qdist_sync(hpgq_qdist_t *qd);
+/* zero the table, the longest read and the too-long state (async) */
+int  hpgq_qdist_reset(hpgq_qdist_t *qd);
+/* hist[p * 256 + b], p < *npos = the longest counted read; n >= *npos * 256
+ * (hist == NULL: size query).  Synchronises. */
+int  hpgq_qdist_read(hpgq_qdist_t *qd, uint64_t *hist, size_t n, int32_t *npos);
+/* Tests only: at most max_wg workgroups (0, the default: no limit), so that a
+ * small batch gives every workgroup several read groups. */
+int  hpgq_qdist_debug_set_max_workgroups(hpgq_qdist_t *qd, int max_wg);
+/* Host only, no device (csrc/hpgq_qdist_post.cpp).
+ * dst[p][b] += src[p][b] for p < npos_src: merges shards' tables
+ * (HPGQ_E_INVALID if npos_src > npos_dst). */
+int  hpgq_qdist_add(uint64_t *dst, int npos_dst, const uint64_t *src, int npos_src);
+/* Per position p: c = the row sum; the num/den quantile is the smallest Q, in
+ * ascending signed order (bytes 128..255 before 0..127), whose cumulative
+ * count reaches the rank max(1, ceil(num c / den)), exact for every u64 c;
+ * rows[p] = {c, min, 1/10, 1/4, 1/2, 3/4, 9/10, max}, all zeros when c == 0. */
+int  hpgq_qdist_quantiles(const uint64_t *hist, int npos, int phred, hpgq_qdist_row_t *rows);
 
 /* ---------------------------------------------------------------------- */
 /* FASTQ text -> device batch (the parsing half of the producer's          */
