@@ -78,6 +78,16 @@ int main(int argc, char **argv) {
     }
     if (f) fclose(f);
   }
+  if (o->duplication_out && r.dup_on) {   /* per mate: [n u64 | n keys ascending | n counts in key order] */
+    FILE *f = fopen(o->duplication_out, "wb");
+    for (int m = 0; m < (p.paired ? 2 : 1); ++m) {
+      const uint64_t n = (uint64_t)r.dup_n[m];
+      if (!f || fwrite(&n, sizeof(uint64_t), 1, f) != 1 || fwrite(r.dup_keys[m], sizeof(uint64_t), n, f) != n ||
+          fwrite(r.dup_counts[m], sizeof(uint64_t), n, f) != n)
+        rc = 1;
+    }
+    if (f) fclose(f);
+  }
   if (o->cg_out && r.cg_seq) {   /* [table_seq | table_q | word count] u32 */
     const size_t cells = (size_t)1 << (2 * o->k_cg);
     FILE *f = fopen(o->cg_out, "wb");
@@ -97,6 +107,9 @@ int main(int argc, char **argv) {
     if (r.qdist[m] &&
         cli_report_qdist(o, &p, r.qdist[m], r.qdist_npos[m], p.paired ? mate_name[m] : cli_base_name(o->in_filename)))
       rc = 1;
+  /* --duplication: one file per mate, named as that mate's report set */
+  for (int m = 0; cmd == CMD_STATS && r.dup_on && m < (p.paired ? 2 : 1); ++m)
+    if (cli_report_dup(o, &r.dup_levels[m], p.paired ? mate_name[m] : cli_base_name(o->in_filename))) rc = 1;
 
   if (!o->quiet) {
     printf("\n\nRESULTS\n");
@@ -144,6 +157,10 @@ int main(int argc, char **argv) {
   free(r.kmers);
   free(r.qdist[0]);
   free(r.qdist[1]);
+  for (int m = 0; m < 2; ++m) {
+    free(r.dup_keys[m]);
+    free(r.dup_counts[m]);
+  }
   free(r.cg_seq);
   free(r.cg_q);
   cli_free(o);

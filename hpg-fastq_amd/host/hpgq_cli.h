@@ -35,6 +35,7 @@ typedef struct {
   int quality_encoding_value;
   int kmers_on;
   int quality_dist_on;      /* stats --quality-dist */
+  int duplication_on;       /* stats --duplication */
   /* chaos game (old/main_hpg_fastq_old.c:185-189: --cg | --chaos-game, --k, --gs-filename) */
   int cg_on, k_cg;
   char *gs_filename;
@@ -57,6 +58,7 @@ typedef struct {
   char *kmers_out;          /* raw u64 k-mer table dump (tests) */
   char *cg_out;             /* raw u32 chaos-game tables dump (tests) */
   char *quality_dist_out;   /* raw [npos u64 | hist] per mate dump (tests) */
+  char *duplication_out;    /* raw [n u64 | keys ascending | counts] per mate dump (tests) */
   int quiet;
   int stream_writer;        /* filter / edit: one writer thread instead of mapped outputs */
   int writer_hook;          /* tests only (--writer-test-hook): hpgq_mapout.h MAPOUT_HOOK_* */
@@ -84,6 +86,10 @@ typedef struct {
   int kmers_npos;
   uint64_t *qdist[2];       /* --quality-dist: per mate hist [qdist_npos][HPGQ_QDIST_VALUES] (malloc'd) */
   int qdist_npos[2];        /* the longest counted read of the mate */
+  int dup_on;               /* --duplication: dup_levels[] hold the mates' levels */
+  hpgq_dup_levels_t dup_levels[2];
+  uint64_t *dup_keys[2], *dup_counts[2];   /* --duplication-out: keys ascending, counts in key order (malloc'd) */
+  size_t dup_n[2];
   uint32_t *cg_seq, *cg_q;  /* --cg: table_seq / table_q [dim*dim] (malloc'd) */
   uint32_t cg_words;        /* fq_word_count */
   int cg_exact_calls;       /* chaos-game calls the exact simulation redid */
@@ -107,6 +113,8 @@ int cli_report_set(const cli_options_t *o, const hpgq_params_t *p, const cli_res
 /* --quality-dist: <base>.quality.dist.per.nt.data from one mate's table */
 int cli_report_qdist(const cli_options_t *o, const hpgq_params_t *p, const uint64_t *hist, int npos,
                      const char *base);
+/* --duplication: <base>.duplication.data from one mate's levels */
+int cli_report_dup(const cli_options_t *o, const hpgq_dup_levels_t *lv, const char *base);
 const char *cli_base_name(const char *path);
 /* the report base names of the two mates: each input's base name, or
  * <base>_1 / <base>_2 for --interleaved (out: 2 x 4096 bytes) */

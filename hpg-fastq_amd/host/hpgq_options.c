@@ -7,7 +7,8 @@
  * Build-specific additions: --fq1 / --fq2 / --interleaved (paired-end input,
  * after old/README), --gpu, --lmax, --chunk-mb, --print-params,
  * --counters-out, --kmers-out, --quiet, and stats --quality-dist /
- * --quality-dist-out.  --quality-encoding is accepted by every command
+ * --quality-dist-out and --duplication / --duplication-out
+ * (§2.9).  --quality-encoding is accepted by every command
  * (quirk Q11).
  */
 #define _GNU_SOURCE
@@ -81,6 +82,7 @@ static void usage(const cli_options_t *o) {
   if (o->command == CMD_STATS) {
     printf("  --kmers                         Enable k-mers analysis (5-mer)\n");
     printf("  --quality-dist                  Quality distribution per read position (quartiles, P10, P90)\n");
+    printf("  --duplication                   Exact sequence duplication levels\n");
     printf("  --cg, --chaos-game              Genomic signature (chaos game) tables and images\n");
     printf("  --k=<int>                       Chaos game word size (1-12, default 7)\n");
     printf("  --gs-filename=<file>            Reference genomic signature: difference table and image\n");
@@ -109,6 +111,8 @@ static void usage(const cli_options_t *o) {
     printf("  --kmers-out=<file>              Write the raw u64 k-mer table [1024][lmax-4]\n");
   if (o->command == CMD_STATS)
     printf("  --quality-dist-out=<file>       Write the raw quality distribution per mate: u64 npos, u64 [npos][256]\n");
+  if (o->command == CMD_STATS)
+    printf("  --duplication-out=<file>        Write the raw duplication table per mate: u64 n, keys [n], counts [n]\n");
   if (o->command == CMD_STATS)
     printf("  --cg-out=<file>              Write the raw u32 chaos-game tables + word count\n");
   if (o->command != CMD_STATS)
@@ -142,7 +146,7 @@ enum {
   O_THREADS = 1000, O_BATCH, O_QENC, O_KMERS, O_LRANGE, O_QRANGE, O_LLEN, O_LQRANGE, O_RLEN,
   O_RQRANGE, O_MAXN, O_MAXOOQ, O_GPU, O_LMAX, O_CHUNK, O_PRINT, O_COUNTERS, O_QUIET,
   O_KMERSOUT, O_CG, O_KCG, O_GS, O_GPUS, O_CGBATCH, O_CGOUT, O_GPUW, O_STREAMW, O_WHOOK, O_COPYT, O_PFT,
-  O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT
+  O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT, O_DUP, O_DUPOUT
 };
 
 cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **argv) {
@@ -201,6 +205,8 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
       {"kmers-out", required_argument, 0, O_KMERSOUT},
       {"quality-dist", no_argument, 0, O_QDIST},
       {"quality-dist-out", required_argument, 0, O_QDISTOUT},
+      {"duplication", no_argument, 0, O_DUP},
+      {"duplication-out", required_argument, 0, O_DUPOUT},
       {"quiet", no_argument, 0, O_QUIET},
       {"stream-writer", no_argument, 0, O_STREAMW},
       {"writer-test-hook", required_argument, 0, O_WHOOK},
@@ -234,6 +240,15 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
         }
         if (c == O_QDIST) o->quality_dist_on = 1;
         else o->quality_dist_out = strdup(optarg);
+        break;
+      case O_DUP:
+      case O_DUPOUT:
+        if (command != CMD_STATS) {   /* one line, before anything is opened or written */
+          fprintf(stderr, "hpg-fastq: --duplication is an option of the stats command, not of %s\n", o->command_name);
+          exit(1);
+        }
+        if (c == O_DUP) o->duplication_on = 1;
+        else o->duplication_out = strdup(optarg);
         break;
       case O_CG:
         if (command != CMD_STATS) usage(o);
@@ -400,6 +415,7 @@ void cli_display(const cli_options_t *o) {
   printf("\tOutput dirname       : %s\n", o->out_dirname);
   printf("\tQuality encoding     : %s\n", o->quality_encoding_name);
   if (o->quality_dist_on) printf("\tQuality distribution : per read position (--quality-dist)\n");
+  if (o->duplication_on) printf("\tDuplication levels   : exact, per sequence (--duplication)\n");
   printf("\n%s options\n", o->command == CMD_EDIT ? "Edit and filter" : "Filter");
   int shown = 0;
   if (o->read_length_range) printf("\tRead length range   : %s\n", o->read_length_range), shown++;
@@ -508,6 +524,7 @@ void cli_free(cli_options_t *o) {
   free(o->kmers_out);
   free(o->cg_out);
   free(o->quality_dist_out);
+  free(o->duplication_out);
   free(o->gs_filename);
   free(o);
 }

@@ -747,6 +747,61 @@ static void unmap_outputs(pipe_t *P, int *rc) {
   P->map[0] = P->map[1] = NULL;
 }
 
+/* --duplication: a worker's table starts at 16 MB and doubles as the input
+ * needs, up to 64 GB (hpgq_dup_open) */
+#define DUP_LOG2_SLOTS 20
+#define DUP_LOG2_MAX_SLOTS 32
+
+/* all of src's pairs on the host (malloc'd; *n == 0: both NULL) */
+static int dup_pairs(hpgq_dup_t *src, uint64_t **keys, uint64_t **counts, size_t *n) {
+  *keys = *counts = NULL;
+  int rc = hpgq_dup_export(src, NULL, NULL, 0, n);
+  if (rc || *n == 0) return rc;
+  *keys = malloc(*n * sizeof(uint64_t));
+  *counts = malloc(*n * sizeof(uint64_t));
+  if (!*keys || !*counts) rc = HPGQ_E_NOMEM;
+  if (rc == 0) rc = hpgq_dup_export(src, *keys, *counts, *n, n);
+  if (rc) {
+    free(*keys);
+    free(*counts);
+    *keys = *counts = NULL;
+  }
+  return rc;
+}
+
+/* dst += src through the host: works between GPUs too */
+static int dup_move(hpgq_dup_t *dst, hpgq_dup_t *src) {
+  uint64_t *keys, *counts;
+  size_t n = 0;
+  int rc = dup_pairs(src, &keys, &counts, &n);
+  if (rc == 0 && n) rc = hpgq_dup_import(dst, keys, counts, n);
+  free(keys);
+  free(counts);
+  return rc;
+}
+
+typedef struct { uint64_t key, count; } dup_pair_t;
+static int dup_pair_cmp(const void *a, const void *b) {
+  const uint64_t x = ((const dup_pair_t *)a)->key, y = ((const dup_pair_t *)b)->key;
+  return x < y ? -1 : x > y;
+}
+
+/* the table with its keys ascending */
+static int dup_sorted(hpgq_dup_t *src, uint64_t **keys, uint64_t **counts, size_t *n) {
+  int rc = dup_pairs(src, keys, counts, n);
+  if (rc || *n == 0) return rc;
+  dup_pair_t *pr = malloc(*n * sizeof(*pr));
+  if (!pr) return HPGQ_E_NOMEM;   /* (the caller frees the arrays with its result) */
+  for (size_t i = 0; i < *n; ++i) pr[i] = (dup_pair_t){(*keys)[i], (*counts)[i]};
+  qsort(pr, *n, sizeof(*pr), dup_pair_cmp);
+  for (size_t i = 0; i < *n; ++i) {
+    (*keys)[i] = pr[i].key;
+    (*counts)[i] = pr[i].count;
+  }
+  free(pr);
+  return 0;
+}
+
 /* one GPU worker: its own ctx, parser, k-mer and CGR accumulators on one device */
 typedef struct {
   pipe_t *P;
@@ -756,6 +811,7 @@ typedef struct {
   hpgq_parser_t *ps[2];   /* one per side ([1]: --fq2), both on the ctx stream */
   hpgq_kmers_t *km;
   hpgq_qdist_t *qd[2];    /* --quality-dist: one table per mate, on the ctx stream */
+  hpgq_dup_t *dp[2];      /* --duplication: one hash table per mate, on the ctx stream */
   hpgq_cgr_t *cg;
   uint8_t *d_mask;
   uint32_t *d_trim;
@@ -778,6 +834,9 @@ static int worker_open(worker_t *W) {
    * input): lmax rows to start with, the window of on-chip values from phred */
   for (int m = 0; m < W->P->nmates && rc == 0 && o->quality_dist_on; ++m)
     rc = hpgq_qdist_open(&W->qd[m], W->device, W->p->lmax, W->p->phred, hpgq_stream(W->ctx));
+  /* --duplication counts the same reads again, per mate, by their sequence */
+  for (int m = 0; m < W->P->nmates && rc == 0 && o->duplication_on; ++m)
+    rc = hpgq_dup_open(&W->dp[m], W->device, DUP_LOG2_SLOTS, DUP_LOG2_MAX_SLOTS, hpgq_stream(W->ctx));
   /* --cg: chaos_game_fill_tables per batch (= chunk), the base quality from
    * --quality-encoding; with a filter only the passed reads (ONLY_VALID_READS
    * with the mask as read_status, old/chaos_game.c:188) */
@@ -793,6 +852,8 @@ static void worker_close(worker_t *W) {
   hpgq_kmers_close(W->km);
   hpgq_qdist_close(W->qd[0]);
   hpgq_qdist_close(W->qd[1]);
+  hpgq_dup_close(W->dp[0]);
+  hpgq_dup_close(W->dp[1]);
   hpgq_cgr_close(W->cg);
   hpgq_close(W->ctx);
 }
@@ -819,7 +880,7 @@ static int worker_chunk(worker_t *W, slot_t *s) {
   const int nm = P->nmates, ns = P->nsides;
   const int writes = o->command != CMD_STATS;
   const int edit = o->command == CMD_EDIT;
-  const int need_mask = writes || ((W->km || W->cg || W->qd[0]) && o->filter_on);
+  const int need_mask = writes || ((W->km || W->cg || W->qd[0] || W->dp[0]) && o->filter_on);
   const char *const text[2] = {s->buf, s->buf2};
   const size_t use[2] = {s->use, s->use2};
   hpgq_batch_t b[2];
@@ -869,6 +930,8 @@ static int worker_chunk(worker_t *W, slot_t *s) {
   if (rc == 0 && W->km) rc = hpgq_kmers_count_device(W->km, &b[0], o->filter_on ? W->d_mask : NULL);
   for (int m = 0; m < nm && rc == 0 && W->qd[m]; ++m)   /* (paired: the pair mask for both mates) */
     rc = hpgq_qdist_count_device(W->qd[m], &b[m], o->filter_on ? W->d_mask : NULL);
+  for (int m = 0; m < nm && rc == 0 && W->dp[m]; ++m)   /* (the same reads, the same mask) */
+    rc = hpgq_dup_count_device(W->dp[m], &b[m], o->filter_on ? W->d_mask : NULL);
   if (rc == 0 && writes) {
     s->nreads = b[0].num_reads;
     if (ensure_results(s, b[0].num_reads, nm)) rc = HPGQ_E_NOMEM;
@@ -1147,6 +1210,16 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
       if (rc == 0) rc = hpgq_qdist_add(res->qdist[m], np, part, pw);
     }
     free(part);
+  }
+  /* --duplication: per mate, every other worker's table exported and imported
+   * into worker 0's (levels of shards cannot be added: one sequence may be in
+   * several), then the levels, and for --duplication-out the table itself */
+  for (int m = 0; m < nm && rc == 0 && o->duplication_on; ++m) {
+    for (int w = 1; w < G && rc == 0; ++w) rc = dup_move(W[0].dp[m], W[w].dp[m]);
+    if (rc == 0) rc = hpgq_dup_levels(W[0].dp[m], &res->dup_levels[m]);
+    if (rc == 0 && o->duplication_out)
+      rc = dup_sorted(W[0].dp[m], &res->dup_keys[m], &res->dup_counts[m], &res->dup_n[m]);
+    res->dup_on = rc == 0;
   }
   if (rc == 0 && o->cg_on) {
     const size_t cells = (size_t)1 << (2 * o->k_cg);

@@ -30,7 +30,9 @@ ERRORS = {0: "ok", -1: "invalid argument", -2: "HIP runtime error", -3: "out of 
           -10: "mate pairs out of step"}
 E_FORMAT, E_PAIRING = -8, -10
 E_READ_TOO_LONG = -4
+E_INVALID, E_NOMEM, E_STATE = -1, -3, -7
 QDIST_VALUES = 256
+DUP_LEVELS = 16
 
 
 class HpgqError(RuntimeError):
@@ -86,6 +88,11 @@ class Summary(C.Structure):
 class QdistRow(C.Structure):
     _fields_ = [("count", C.c_uint64)] + [(f, C.c_int32) for f in
                                           ("min", "p10", "q1", "median", "q3", "p90", "max")]
+
+
+class DupLevels(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("distinct", C.c_uint64), ("max_count", C.c_uint64),
+                ("distinct_at", C.c_uint64 * DUP_LEVELS), ("reads_at", C.c_uint64 * DUP_LEVELS)]
 
 
 class GsInfo(C.Structure):
@@ -189,6 +196,22 @@ _SIGS = [
     ("hpgq_qdist_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
     ("hpgq_qdist_add", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     ("hpgq_qdist_quantiles", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ("hpgq_dup_open", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("hpgq_dup_close", None, [C.c_void_p]),
+    ("hpgq_dup_reset", C.c_int, [C.c_void_p]),
+    ("hpgq_dup_count_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p]),
+    ("hpgq_dup_sync", C.c_int, [C.c_void_p]),
+    ("hpgq_dup_levels", C.c_int, [C.c_void_p, C.POINTER(DupLevels)]),
+    ("hpgq_dup_export", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("hpgq_dup_import", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("hpgq_dup_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
+    ("hpgq_dup_debug_fingerprints", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p]),
+    ("hpgq_dup_debug_set_timing", C.c_int, [C.c_void_p, C.c_int]),
+    ("hpgq_dup_debug_last_times", C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    ("hpgq_dup_debug_info", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int64)]),
+    ("hpgq_dup_fingerprint", C.c_uint64, [C.c_char_p, C.c_size_t]),
+    ("hpgq_dup_level_bound", C.c_uint64, [C.c_int]),
+    ("hpgq_dup_levels_of", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(DupLevels)]),
     ("hpgq_synth_length", C.c_int32, [C.POINTER(Synth), C.c_int64]),
     ("hpgq_synth_indices_host", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p]),
     ("hpgq_synth_device", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p,

@@ -9,8 +9,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, counters_len, CGR_ALL_READS, ROUTES,
-                   E_PAIRING, QDIST_VALUES)
+from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, counters_len, CGR_ALL_READS,
+                   ROUTES, E_PAIRING, QDIST_VALUES, DUP_LEVELS)
 
 # Kernel route for new Engines (tests / A/B: a key of ROUTES, or None for the
 # library's automatic chain).  Applied through hpgq_debug_set_route: the
@@ -449,6 +449,116 @@ def qdist_quantiles(hist, phred):
         out[p, 1:] = (r.min, r.p10, r.q1, r.median, r.q3, r.p90, r.max)
         out.view(np.uint64)[p, 0] = r.count   # (a count of 2^63 or more: its two's complement)
     return out
+
+
+def _levels_dict(lv):
+    return dict(reads=int(lv.reads), distinct=int(lv.distinct), max_count=int(lv.max_count),
+                distinct_at=[int(x) for x in lv.distinct_at], reads_at=[int(x) for x in lv.reads_at])
+
+
+class Duplication:
+    """hpgq_dup: `stats --duplication`, the multiset {fingerprint -> count} of
+    the counted reads' sequences in a device hash table.  The
+    table starts at 2^log2_slots slots and doubles up to 2^log2_max_slots."""
+
+    def __init__(self, log2_slots=20, log2_max_slots=32, device=0, stream=None):
+        self._h = None
+        h = C.c_void_p()
+        check(lib.hpgq_dup_open(C.byref(h), device, log2_slots, log2_max_slots, stream), "hpgq_dup_open")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib.hpgq_dup_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def count_device(self, batch, mask_ptr=None):
+        """HpgqError -3 when the table would have to grow past 2^log2_max_slots."""
+        check(lib.hpgq_dup_count_device(self._h, C.byref(batch), mask_ptr), "hpgq_dup_count_device")
+
+    def sync(self):
+        check(lib.hpgq_dup_sync(self._h), "hpgq_dup_sync")
+
+    def reset(self):
+        check(lib.hpgq_dup_reset(self._h), "hpgq_dup_reset")
+
+    def set_max_workgroups(self, max_wg):
+        check(lib.hpgq_dup_debug_set_max_workgroups(self._h, max_wg), "hpgq_dup_debug_set_max_workgroups")
+
+    def levels(self):
+        """dict: reads, distinct, max_count, distinct_at[16], reads_at[16] (synchronises)."""
+        lv = DupLevels()
+        check(lib.hpgq_dup_levels(self._h, C.byref(lv)), "hpgq_dup_levels")
+        return _levels_dict(lv)
+
+    def export(self):
+        """(keys, counts): u64 arrays, the keys ascending (synchronises)."""
+        n = C.c_size_t(0)
+        check(lib.hpgq_dup_export(self._h, None, None, 0, C.byref(n)), "hpgq_dup_export")
+        keys = np.zeros(n.value, dtype=np.uint64)
+        counts = np.zeros(n.value, dtype=np.uint64)
+        check(lib.hpgq_dup_export(self._h, _ptr(keys), _ptr(counts), n.value, C.byref(n)), "hpgq_dup_export")
+        order = np.argsort(keys, kind="stable")
+        return keys[order], counts[order]
+
+    def import_(self, keys, counts):
+        """Add counts[i] to the count of keys[i]: the merge of shards' tables."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        if keys.ndim != 1 or keys.shape != counts.shape:
+            raise ValueError("keys and counts are u64 vectors of one length")
+        check(lib.hpgq_dup_import(self._h, _ptr(keys), _ptr(counts), keys.size), "hpgq_dup_import")
+
+    def set_timing(self, on=True):
+        check(lib.hpgq_dup_debug_set_timing(self._h, int(on)), "hpgq_dup_debug_set_timing")
+
+    def last_times(self):
+        """Measurement: (fingerprint kernel us, insert kernel us) of the last count_device."""
+        a, b = C.c_float(0), C.c_float(0)
+        check(lib.hpgq_dup_debug_last_times(self._h, C.byref(a), C.byref(b)), "hpgq_dup_debug_last_times")
+        return a.value, b.value
+
+    def info(self):
+        """Tests: (log2 of the slots now, growths since the table was opened)."""
+        k, r = C.c_int(0), C.c_int64(0)
+        check(lib.hpgq_dup_debug_info(self._h, C.byref(k), C.byref(r)), "hpgq_dup_debug_info")
+        return k.value, r.value
+
+    def fingerprints(self, batch):
+        """Tests: the fingerprint of every read of a device batch, nothing inserted."""
+        out = np.zeros(batch.num_reads, dtype=np.uint64)
+        check(lib.hpgq_dup_debug_fingerprints(self._h, C.byref(batch), _ptr(out)), "hpgq_dup_debug_fingerprints")
+        return out
+
+
+def dup_fingerprint(data):
+    """hpgq_dup_fingerprint: the 64-bit fingerprint of a sequence's bytes."""
+    data = bytes(data)
+    return int(lib.hpgq_dup_fingerprint(data, len(data)))
+
+
+def dup_level_bounds():
+    return [int(lib.hpgq_dup_level_bound(i)) for i in range(DUP_LEVELS)]
+
+
+def dup_levels_of(counts):
+    """hpgq_dup_levels_of: the levels of a list of counts (host only)."""
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    lv = DupLevels()
+    check(lib.hpgq_dup_levels_of(_ptr(counts), counts.size, C.byref(lv)), "hpgq_dup_levels_of")
+    return _levels_dict(lv)
 
 
 class Signature:

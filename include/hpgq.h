@@ -603,6 +603,79 @@ int  hpgq_qdist_add(uint64_t *dst, int npos_dst, const uint64_t *src, int npos_s
 int  hpgq_qdist_quantiles(const uint64_t *hist, int npos, int phred, hpgq_qdist_row_t *rows);
 
 /* ---------------------------------------------------------------------- */
+/* stats --duplication: exact sequence duplication levels                   */
+/* ---------------------------------------------------------------------- */
+
+/*
+ * Build-defined.  Every counted read adds 1 to the count of
+ * its sequence's 64-bit fingerprint (hpgq_dup_fingerprint; never 0) in an
+ * open-addressing table in device memory: the multiset {fingerprint -> count},
+ * count u64.  Two reads are the same sequence iff their fingerprints are
+ * equal; the bytes are compared as they stand.  The levels are read from the
+ * table; shards are merged through hpgq_dup_export / hpgq_dup_import, never by
+ * adding levels (one sequence may be in both).
+ *
+ * The table has 2^log2_slots slots of 16 bytes and doubles as often as needed
+ * to stay at most half full, up to 2^log2_max_slots; a call that would need
+ * more returns HPGQ_E_NOMEM and leaves the table as it was.
+ */
+typedef struct hpgq_dup hpgq_dup_t;
+#define HPGQ_DUP_LEVELS 16
+/* lower bounds 1..10, 50, 100, 500, 1000, 5000, 10000: level i holds the
+ * counts in [lo_i, lo_{i+1}), the last one unbounded (hpgq_dup_level_bound) */
+typedef struct hpgq_dup_levels {
+  uint64_t reads;                          /* sum of the counts                     */
+  uint64_t distinct;                       /* sequences (occupied slots)            */
+  uint64_t max_count;                      /* the highest count                     */
+  uint64_t distinct_at[HPGQ_DUP_LEVELS];   /* sequences at each level               */
+  uint64_t reads_at[HPGQ_DUP_LEVELS];      /* the reads they account for            */
+} hpgq_dup_levels_t;
+
+/* 4 <= log2_slots <= log2_max_slots <= 34; stream: as hpgq_kmers_open.
+ * HPGQ_E_INVALID before any device call. */
+int  hpgq_dup_open(hpgq_dup_t **d, int device, int log2_slots, int log2_max_slots, void *stream);
+void hpgq_dup_close(hpgq_dup_t *d);
+/* empty the table and clear the error word (async; the slots stay allocated) */
+int  hpgq_dup_reset(hpgq_dup_t *d);
+/* Count a DEVICE batch, async; only `seq` and `data_indices` are read (seq
+ * readable HPGQ_DEVICE_SLACK bytes past the data end, any alignment, absolute
+ * offsets); reads of any length, 0 included.  mask (device, may be NULL): only
+ * reads with mask[i] == 1 are counted.  Synchronises only when the table may
+ * have to grow.  HPGQ_E_NOMEM past log2_max_slots (nothing of the batch is
+ * counted). */
+int  hpgq_dup_count_device(hpgq_dup_t *d, const hpgq_batch_t *b, const uint8_t *mask);
+/* waits for the stream; HPGQ_E_STATE if a kernel found the table full (sticky
+ * until hpgq_dup_reset; the host's load bound makes it unreachable) */
+int  hpgq_dup_sync(hpgq_dup_t *d);
+/* the levels of the table, binned on the device.  Synchronises. */
+int  hpgq_dup_levels(hpgq_dup_t *d, hpgq_dup_levels_t *out);
+/* The occupied slots, compacted on the device, in no particular order: *n
+ * pairs (keys == NULL or counts == NULL: size query; cap < *n:
+ * HPGQ_E_INVALID).  Synchronises. */
+int  hpgq_dup_export(hpgq_dup_t *d, uint64_t *keys, uint64_t *counts, size_t cap, size_t *n);
+/* Add n HOST pairs to the table (counts[i] to the count of keys[i]): the merge
+ * of workers, GPUs and ranks.  A key or a count of 0 is HPGQ_E_INVALID. */
+int  hpgq_dup_import(hpgq_dup_t *d, const uint64_t *keys, const uint64_t *counts, size_t n);
+/* Tests only: at most max_wg workgroups per kernel (0, the default: no limit). */
+int  hpgq_dup_debug_set_max_workgroups(hpgq_dup_t *d, int max_wg);
+/* Tests only: the fingerprint of every read of a device batch (no mask, no
+ * insertion) to out_host[num_reads].  Synchronises. */
+int  hpgq_dup_debug_fingerprints(hpgq_dup_t *d, const hpgq_batch_t *b, uint64_t *out_host);
+/* Measurement only (tools/dup_rate.py): with on != 0 every hpgq_dup_count_device
+ * records HIP events around its two kernels; hpgq_dup_debug_last_times waits
+ * for them and gives the fingerprint and the insert kernel's time of the last
+ * call's last launch in microseconds (HPGQ_E_STATE when none was recorded). */
+int  hpgq_dup_debug_set_timing(hpgq_dup_t *d, int on);
+int  hpgq_dup_debug_last_times(hpgq_dup_t *d, float *fp_us, float *insert_us);
+/* Tests only: the table's size now and how often it has grown since it was opened. */
+int  hpgq_dup_debug_info(hpgq_dup_t *d, int *log2_slots, int64_t *rehashes);
+/* Host only, no device (csrc/hpgq_dup_post.cpp). */
+uint64_t hpgq_dup_fingerprint(const void *s, size_t n);
+uint64_t hpgq_dup_level_bound(int level);   /* 0 outside 0 .. HPGQ_DUP_LEVELS - 1 */
+/* the levels of n counts (zeros are no sequence; sums mod 2^64) */
+int  hpgq_dup_levels_of(const uint64_t *counts, size_t n, hpgq_dup_levels_t *out);
+
+/* ---------------------------------------------------------------------- */
 /* FASTQ text -> device batch (the parsing half of the producer's          */
 /* fastq_fread_se, src/stats_fastq.c:183, moved onto the GPU)              */
 /* ---------------------------------------------------------------------- */
