@@ -1,8 +1,14 @@
 // hpgq_dup_post.cpp — host side of `stats --duplication`: the
-// fingerprint of one sequence and the levels of a list of counts.  HIP-free,
-// no device.  The kernels (csrc/hpgq_dup.hip) compute the same two things.
+// fingerprint of one sequence and the levels of a list of counts, and of
+// `stats --overrepresented` (§2.10): the most frequent of a list of (key, count)
+// pairs.  HIP-free, no device.  The kernels (csrc/hpgq_dup.hip) compute the
+// first two; hpgq_dup_top sorts its candidates with the third.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <new>
+#include <utility>
+#include <vector>
 
 #include "../../include/hpgq.h"
 
@@ -51,6 +57,31 @@ int hpgq_dup_levels_of(const uint64_t *counts, size_t n, hpgq_dup_levels_t *out)
     out->distinct += 1;
     out->reads += c;
     if (c > out->max_count) out->max_count = c;
+  }
+  return HPGQ_OK;
+}
+
+int hpgq_dup_top_of(const uint64_t *keys, const uint64_t *counts, size_t n, uint64_t min_count, uint64_t *out_keys,
+                    uint64_t *out_counts, size_t cap, size_t *total) {
+  if (!total || min_count < 1 || (n > 0 && (!keys || !counts)) || (out_keys && !out_counts)) return HPGQ_E_INVALID;
+  try {
+    std::vector<std::pair<uint64_t, uint64_t>> hit;   // (count, key)
+    for (size_t i = 0; i < n; ++i)
+      if (keys[i] && counts[i] >= min_count) hit.emplace_back(counts[i], keys[i]);
+    *total = hit.size();
+    if (!out_keys) return HPGQ_OK;
+    const size_t take = std::min(cap, hit.size());
+    // count descending, ties by key ascending
+    std::partial_sort(hit.begin(), hit.begin() + take, hit.end(),
+                      [](const std::pair<uint64_t, uint64_t> &a, const std::pair<uint64_t, uint64_t> &b) {
+                        return a.first != b.first ? a.first > b.first : a.second < b.second;
+                      });
+    for (size_t i = 0; i < take; ++i) {
+      out_keys[i] = hit[i].second;
+      out_counts[i] = hit[i].first;
+    }
+  } catch (const std::bad_alloc &) {
+    return HPGQ_E_NOMEM;
   }
   return HPGQ_OK;
 }

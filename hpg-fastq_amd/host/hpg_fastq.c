@@ -47,6 +47,17 @@ int main(int argc, char **argv) {
 
   cli_result_t r;
   int rc = cli_run(o, &p, &r);
+  if (rc && r.overrep_error) {   /* one line each */
+    if (r.overrep_error == 1)
+      fprintf(stderr,
+              "hpg-fastq: --overrepresented: the sequences that reached the minimum count need more than %lu bytes; "
+              "raise --overrepresented-min-count or --overrepresented-bytes\n", (unsigned long)o->overrep_bytes);
+    else
+      fprintf(stderr, "hpg-fastq: --overrepresented: internal error: no table kept a listed sequence\n");
+    free(r.counters);
+    cli_free(o);
+    return 1;
+  }
   if (rc) {
     /* one line with the first bad pair (0-based, over the whole input), and the two names of a mismatch */
     if (rc == HPGQ_E_PAIRING && r.pairing_msg[0]) fprintf(stderr, "hpg-fastq: pairing error at %s\n", r.pairing_msg);
@@ -110,6 +121,11 @@ int main(int argc, char **argv) {
   /* --duplication: one file per mate, named as that mate's report set */
   for (int m = 0; cmd == CMD_STATS && r.dup_on && m < (p.paired ? 2 : 1); ++m)
     if (cli_report_dup(o, &r.dup_levels[m], p.paired ? mate_name[m] : cli_base_name(o->in_filename))) rc = 1;
+  /* --overrepresented: one file per mate, named as that mate's report set */
+  for (int m = 0; cmd == CMD_STATS && r.overrep_on && m < (p.paired ? 2 : 1); ++m)
+    if (cli_report_overrep(o, r.overrep_n[m], r.overrep_counts[m], r.overrep_lens[m], r.overrep_seqs[m], r.overrep_reads[m],
+                           p.paired ? mate_name[m] : cli_base_name(o->in_filename)))
+      rc = 1;
 
   if (!o->quiet) {
     printf("\n\nRESULTS\n");
@@ -160,6 +176,10 @@ int main(int argc, char **argv) {
   for (int m = 0; m < 2; ++m) {
     free(r.dup_keys[m]);
     free(r.dup_counts[m]);
+    for (size_t i = 0; r.overrep_seqs[m] && i < r.overrep_n[m]; ++i) free(r.overrep_seqs[m][i]);
+    free(r.overrep_seqs[m]);
+    free(r.overrep_counts[m]);
+    free(r.overrep_lens[m]);
   }
   free(r.cg_seq);
   free(r.cg_q);

@@ -36,6 +36,10 @@ typedef struct {
   int kmers_on;
   int quality_dist_on;      /* stats --quality-dist */
   int duplication_on;       /* stats --duplication */
+  int overrep_on;           /* stats --overrepresented */
+  uint64_t overrep_min_count;   /* K: the merged count a listed sequence has at least */
+  int overrep_top;          /* N: sequences listed at most */
+  uint64_t overrep_bytes;   /* the arena of every worker's table */
   /* chaos game (old/main_hpg_fastq_old.c:185-189: --cg | --chaos-game, --k, --gs-filename) */
   int cg_on, k_cg;
   char *gs_filename;
@@ -90,6 +94,14 @@ typedef struct {
   hpgq_dup_levels_t dup_levels[2];
   uint64_t *dup_keys[2], *dup_counts[2];   /* --duplication-out: keys ascending, counts in key order (malloc'd) */
   size_t dup_n[2];
+  /* --overrepresented: per mate the listed sequences, count descending (all malloc'd);
+   * overrep_reads[] the merged table's total */
+  int overrep_on;
+  int overrep_error;        /* 1: a worker's arena was too small, 2: no table kept a listed sequence */
+  size_t overrep_n[2];
+  uint64_t *overrep_counts[2], *overrep_lens[2];
+  unsigned char **overrep_seqs[2];
+  uint64_t overrep_reads[2];
   uint32_t *cg_seq, *cg_q;  /* --cg: table_seq / table_q [dim*dim] (malloc'd) */
   uint32_t cg_words;        /* fq_word_count */
   int cg_exact_calls;       /* chaos-game calls the exact simulation redid */
@@ -115,6 +127,9 @@ int cli_report_qdist(const cli_options_t *o, const hpgq_params_t *p, const uint6
                      const char *base);
 /* --duplication: <base>.duplication.data from one mate's levels */
 int cli_report_dup(const cli_options_t *o, const hpgq_dup_levels_t *lv, const char *base);
+/* --overrepresented: <base>.overrepresented.data, n sequences in rank order */
+int cli_report_overrep(const cli_options_t *o, size_t n, const uint64_t *counts, const uint64_t *lens,
+                       unsigned char *const *seqs, uint64_t reads, const char *base);
 const char *cli_base_name(const char *path);
 /* the report base names of the two mates: each input's base name, or
  * <base>_1 / <base>_2 for --interleaved (out: 2 x 4096 bytes) */

@@ -7,7 +7,8 @@
  * Build-specific additions: --fq1 / --fq2 / --interleaved (paired-end input,
  * after old/README), --gpu, --lmax, --chunk-mb, --print-params,
  * --counters-out, --kmers-out, --quiet, and stats --quality-dist /
- * --quality-dist-out and --duplication / --duplication-out
+ * --quality-dist-out, --overrepresented and its value flags
+ *  and --duplication / --duplication-out
  * (§2.9).  --quality-encoding is accepted by every command
  * (quirk Q11).
  */
@@ -83,6 +84,10 @@ static void usage(const cli_options_t *o) {
     printf("  --kmers                         Enable k-mers analysis (5-mer)\n");
     printf("  --quality-dist                  Quality distribution per read position (quartiles, P10, P90)\n");
     printf("  --duplication                   Exact sequence duplication levels\n");
+    printf("  --overrepresented               The most frequent sequences, exact counts over whole reads\n");
+    printf("  --overrepresented-min-count=<int>  List the sequences that occur at least this often (default 100)\n");
+    printf("  --overrepresented-top=<int>     List at most this many sequences (1-100000, default 20)\n");
+    printf("  --overrepresented-bytes=<int>   Device bytes per table for the listed sequences (default 268435456)\n");
     printf("  --cg, --chaos-game              Genomic signature (chaos game) tables and images\n");
     printf("  --k=<int>                       Chaos game word size (1-12, default 7)\n");
     printf("  --gs-filename=<file>            Reference genomic signature: difference table and image\n");
@@ -146,8 +151,20 @@ enum {
   O_THREADS = 1000, O_BATCH, O_QENC, O_KMERS, O_LRANGE, O_QRANGE, O_LLEN, O_LQRANGE, O_RLEN,
   O_RQRANGE, O_MAXN, O_MAXOOQ, O_GPU, O_LMAX, O_CHUNK, O_PRINT, O_COUNTERS, O_QUIET,
   O_KMERSOUT, O_CG, O_KCG, O_GS, O_GPUS, O_CGBATCH, O_CGOUT, O_GPUW, O_STREAMW, O_WHOOK, O_COPYT, O_PFT,
-  O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT, O_DUP, O_DUPOUT
+  O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT, O_DUP, O_DUPOUT, O_OVER, O_OVERMIN, O_OVERTOP, O_OVERBYTES
 };
+
+/* a whole-string decimal in [lo, hi] (u64), else the usage error */
+static uint64_t u64_arg(const cli_options_t *o, const char *flag, const char *s, uint64_t lo, uint64_t hi) {
+  char *end = NULL;
+  errno = 0;
+  const unsigned long long v = strtoull(s, &end, 10);
+  if (errno || end == s || *end != '\0' || *s == '-' || v < lo || v > hi) {
+    printf("\nError: --%s must be an integer in %llu..%llu (%s)\n", flag, (unsigned long long)lo, (unsigned long long)hi, s);
+    usage(o);
+  }
+  return (uint64_t)v;
+}
 
 cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **argv) {
   static const char *names[] = {"stats", "filter", "edit"};
@@ -168,6 +185,10 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   o->cg_batch_size = 64000000;   /* DEFAULT_BATCH_SIZE_MB * 1000000, old/main_hpg_fastq_old.c:116 */
   o->gpu_workers = 2;
   o->prefault_threads = -1;
+  o->overrep_min_count = 100;
+  o->overrep_top = 20;
+  o->overrep_bytes = (uint64_t)1 << 28;
+  int overrep_values = 0;   /* a value flag of --overrepresented was given */
   static const struct option longopts[] = {
       {"help", no_argument, 0, 'h'},
       {"fastq-file", required_argument, 0, 'f'},
@@ -207,6 +228,10 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
       {"quality-dist-out", required_argument, 0, O_QDISTOUT},
       {"duplication", no_argument, 0, O_DUP},
       {"duplication-out", required_argument, 0, O_DUPOUT},
+      {"overrepresented", no_argument, 0, O_OVER},
+      {"overrepresented-min-count", required_argument, 0, O_OVERMIN},
+      {"overrepresented-top", required_argument, 0, O_OVERTOP},
+      {"overrepresented-bytes", required_argument, 0, O_OVERBYTES},
       {"quiet", no_argument, 0, O_QUIET},
       {"stream-writer", no_argument, 0, O_STREAMW},
       {"writer-test-hook", required_argument, 0, O_WHOOK},
@@ -249,6 +274,20 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
         }
         if (c == O_DUP) o->duplication_on = 1;
         else o->duplication_out = strdup(optarg);
+        break;
+      case O_OVER:
+      case O_OVERMIN:
+      case O_OVERTOP:
+      case O_OVERBYTES:
+        if (command != CMD_STATS) {   /* one line, before anything is opened or written */
+          fprintf(stderr, "hpg-fastq: --overrepresented is an option of the stats command, not of %s\n", o->command_name);
+          exit(1);
+        }
+        if (c == O_OVER) o->overrep_on = 1;
+        else overrep_values = 1;
+        if (c == O_OVERMIN) o->overrep_min_count = u64_arg(o, "overrepresented-min-count", optarg, 1, UINT64_MAX);
+        if (c == O_OVERTOP) o->overrep_top = count_arg(o, "overrepresented-top", optarg, 1, 100000);
+        if (c == O_OVERBYTES) o->overrep_bytes = u64_arg(o, "overrepresented-bytes", optarg, 1, (uint64_t)1 << 40);
         break;
       case O_CG:
         if (command != CMD_STATS) usage(o);
@@ -299,6 +338,10 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   }
   if (o->interleaved && !o->in_filename) {
     printf("\nError: --interleaved needs the input file (-f)\n");
+    usage(o);
+  }
+  if (overrep_values && !o->overrep_on) {
+    printf("\nError: --overrepresented-min-count, -top and -bytes need --overrepresented\n");
     usage(o);
   }
   if (fq1) o->in_filename = fq1;
@@ -416,6 +459,9 @@ void cli_display(const cli_options_t *o) {
   printf("\tQuality encoding     : %s\n", o->quality_encoding_name);
   if (o->quality_dist_on) printf("\tQuality distribution : per read position (--quality-dist)\n");
   if (o->duplication_on) printf("\tDuplication levels   : exact, per sequence (--duplication)\n");
+  if (o->overrep_on)
+    printf("\tOverrepresented      : top %d with count >= %lu (--overrepresented)\n", o->overrep_top,
+           (unsigned long)o->overrep_min_count);
   printf("\n%s options\n", o->command == CMD_EDIT ? "Edit and filter" : "Filter");
   int shown = 0;
   if (o->read_length_range) printf("\tRead length range   : %s\n", o->read_length_range), shown++;

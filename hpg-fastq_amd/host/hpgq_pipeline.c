@@ -834,9 +834,16 @@ static int worker_open(worker_t *W) {
    * input): lmax rows to start with, the window of on-chip values from phred */
   for (int m = 0; m < W->P->nmates && rc == 0 && o->quality_dist_on; ++m)
     rc = hpgq_qdist_open(&W->qd[m], W->device, W->p->lmax, W->p->phred, hpgq_stream(W->ctx));
-  /* --duplication counts the same reads again, per mate, by their sequence */
-  for (int m = 0; m < W->P->nmates && rc == 0 && o->duplication_on; ++m)
+  /* --duplication counts the same reads again, per mate, by their sequence;
+   * --overrepresented needs the same tables, keeping the bytes of the sequences
+   * that reach ceil(K / workers) in one of them: a sequence with K or more in
+   * all has that many in at least one */
+  for (int m = 0; m < W->P->nmates && rc == 0 && (o->duplication_on || o->overrep_on); ++m) {
     rc = hpgq_dup_open(&W->dp[m], W->device, DUP_LOG2_SLOTS, DUP_LOG2_MAX_SLOTS, hpgq_stream(W->ctx));
+    const uint64_t nw = (uint64_t)W->P->nworkers;
+    if (rc == 0 && o->overrep_on)
+      rc = hpgq_dup_keep_sequences(W->dp[m], o->overrep_min_count / nw + (o->overrep_min_count % nw != 0), o->overrep_bytes);
+  }
   /* --cg: chaos_game_fill_tables per batch (= chunk), the base quality from
    * --quality-encoding; with a filter only the passed reads (ONLY_VALID_READS
    * with the mask as read_status, old/chaos_game.c:188) */
@@ -856,6 +863,41 @@ static void worker_close(worker_t *W) {
   hpgq_dup_close(W->dp[1]);
   hpgq_cgr_close(W->cg);
   hpgq_close(W->ctx);
+}
+
+/* --overrepresented, mate m, after the merge into worker 0's table: the top N
+ * of the merged counts, and each one's bytes from the first worker's table
+ * that kept them (the merge moves counts, never bytes; every arena was found
+ * large enough before the merge, and an import keeps nothing) */
+static int overrep_list(const cli_options_t *o, worker_t *W, int G, int m, cli_result_t *res) {
+  size_t total = 0;
+  const size_t cap = (size_t)o->overrep_top;
+  uint64_t *keys = malloc(cap * sizeof(uint64_t));
+  res->overrep_counts[m] = malloc(cap * sizeof(uint64_t));
+  res->overrep_lens[m] = calloc(cap, sizeof(uint64_t));
+  res->overrep_seqs[m] = calloc(cap, sizeof(unsigned char *));
+  res->overrep_reads[m] = res->dup_levels[m].reads;
+  int rc = keys && res->overrep_counts[m] && res->overrep_lens[m] && res->overrep_seqs[m] ? 0 : HPGQ_E_NOMEM;
+  if (rc == 0) rc = hpgq_dup_top(W[0].dp[m], o->overrep_min_count, keys, res->overrep_counts[m], cap, &total);
+  const size_t n = total < cap ? total : cap;
+  for (size_t i = 0; i < n && rc == 0; ++i) {
+    int64_t len = -1;
+    for (int w = 0; w < G && rc == 0 && len < 0; ++w) {
+      rc = hpgq_dup_sequence(W[w].dp[m], keys[i], NULL, 0, &len);
+      if (rc || len < 0) continue;
+      res->overrep_seqs[m][i] = malloc(len ? (size_t)len : 1);
+      if (!res->overrep_seqs[m][i]) rc = HPGQ_E_NOMEM;
+      else rc = hpgq_dup_sequence(W[w].dp[m], keys[i], res->overrep_seqs[m][i], (size_t)len, &len);
+      res->overrep_lens[m][i] = (uint64_t)len;
+    }
+    if (rc == 0 && len < 0) {   /* no table kept a listed sequence: the shard rule is broken */
+      res->overrep_error = 2;
+      rc = HPGQ_E_STATE;
+    }
+  }
+  if (rc == 0) res->overrep_n[m] = n;
+  free(keys);
+  return rc;
 }
 
 /* the mate name of record r of a text, for the error line */
@@ -1213,13 +1255,21 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
   }
   /* --duplication: per mate, every other worker's table exported and imported
    * into worker 0's (levels of shards cannot be added: one sequence may be in
-   * several), then the levels, and for --duplication-out the table itself */
-  for (int m = 0; m < nm && rc == 0 && o->duplication_on; ++m) {
+   * several), then the levels, and for --duplication-out the table itself;
+   * --overrepresented takes its list from the merged table (overrep_list) */
+  for (int m = 0; m < nm && rc == 0 && (o->duplication_on || o->overrep_on); ++m) {
+    /* (a representative that did not fit in a worker's arena: HPGQ_E_NOMEM here) */
+    for (int w = 0; w < G && rc == 0 && o->overrep_on; ++w) {
+      rc = hpgq_dup_sync(W[w].dp[m]);
+      if (rc == HPGQ_E_NOMEM) res->overrep_error = 1;
+    }
     for (int w = 1; w < G && rc == 0; ++w) rc = dup_move(W[0].dp[m], W[w].dp[m]);
     if (rc == 0) rc = hpgq_dup_levels(W[0].dp[m], &res->dup_levels[m]);
     if (rc == 0 && o->duplication_out)
       rc = dup_sorted(W[0].dp[m], &res->dup_keys[m], &res->dup_counts[m], &res->dup_n[m]);
-    res->dup_on = rc == 0;
+    res->dup_on = rc == 0 && o->duplication_on;
+    if (rc == 0 && o->overrep_on) rc = overrep_list(o, W, G, m, res);
+    res->overrep_on = rc == 0 && o->overrep_on;
   }
   if (rc == 0 && o->cg_on) {
     const size_t cells = (size_t)1 << (2 * o->k_cg);

@@ -14,7 +14,7 @@ from ._abi import (  # noqa: F401
     counters_len, layout, check, params_default, exported_symbols, E_FORMAT, E_PAIRING,
 )
 from .engine import Engine, ChaosGame, Kmers, Parser, Signature, QualityDist, qdist_add, qdist_quantiles, summary, complete_prefix, record_prefix  # noqa: F401
-from .engine import Duplication, dup_fingerprint, dup_levels_of, dup_level_bounds  # noqa: F401
+from .engine import Duplication, dup_fingerprint, dup_levels_of, dup_level_bounds, dup_top_of  # noqa: F401
 from .engine import (cgr_write_gs, cgr_load_gs, cgr_table_dif, cgr_dif_stats,  # noqa: F401
                      cgr_normalize_quality, cgr_write_pgm, cgr_write_images)
 from .options import parse_range, filter_params, edit_params, stats_params  # noqa: F401

@@ -212,6 +212,13 @@ _SIGS = [
     ("hpgq_dup_fingerprint", C.c_uint64, [C.c_char_p, C.c_size_t]),
     ("hpgq_dup_level_bound", C.c_uint64, [C.c_int]),
     ("hpgq_dup_levels_of", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(DupLevels)]),
+    ("hpgq_dup_keep_sequences", C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    ("hpgq_dup_top", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("hpgq_dup_sequence", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.POINTER(C.c_int64)]),
+    ("hpgq_dup_debug_kept", C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("hpgq_dup_debug_last_keep_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    ("hpgq_dup_top_of", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                  C.POINTER(C.c_size_t)]),
     ("hpgq_synth_length", C.c_int32, [C.POINTER(Synth), C.c_int64]),
     ("hpgq_synth_indices_host", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p]),
     ("hpgq_synth_device", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p,

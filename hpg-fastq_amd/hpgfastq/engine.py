@@ -530,6 +530,51 @@ class Duplication:
         check(lib.hpgq_dup_debug_last_times(self._h, C.byref(a), C.byref(b)), "hpgq_dup_debug_last_times")
         return a.value, b.value
 
+    def keep_sequences(self, min_count, arena_bytes=1 << 28):
+        """Keeping mode: from now on the bytes of every sequence
+        whose count in this table reaches min_count are kept, once, in a device
+        arena of arena_bytes.  Only on an empty table; 0 turns it off."""
+        check(lib.hpgq_dup_keep_sequences(self._h, min_count, arena_bytes), "hpgq_dup_keep_sequences")
+
+    def count_at_least(self, min_count=1):
+        """How many sequences have count >= min_count (synchronises)."""
+        total = C.c_size_t(0)
+        check(lib.hpgq_dup_top(self._h, min_count, None, None, 0, C.byref(total)), "hpgq_dup_top")
+        return total.value
+
+    def top(self, n, min_count=1):
+        """(keys, counts): the n most frequent sequences with count >= min_count,
+        count descending, ties by key ascending (synchronises)."""
+        n = min(int(n), self.count_at_least(min_count))
+        keys = np.zeros(n, dtype=np.uint64)
+        counts = np.zeros(n, dtype=np.uint64)
+        total = C.c_size_t(0)
+        check(lib.hpgq_dup_top(self._h, min_count, _ptr(keys), _ptr(counts), n, C.byref(total)), "hpgq_dup_top")
+        return keys, counts
+
+    def sequence(self, key):
+        """The bytes kept for key in this table, or None (synchronises).
+        HpgqError -3 after a representative did not fit in the arena."""
+        n = C.c_int64(0)
+        check(lib.hpgq_dup_sequence(self._h, key, None, 0, C.byref(n)), "hpgq_dup_sequence")
+        if n.value < 0:
+            return None
+        buf = C.create_string_buffer(max(n.value, 1))
+        check(lib.hpgq_dup_sequence(self._h, key, buf, n.value, C.byref(n)), "hpgq_dup_sequence")
+        return buf.raw[:n.value]
+
+    def kept(self):
+        """Tests: (representatives held, the sum of their lengths)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        check(lib.hpgq_dup_debug_kept(self._h, C.byref(a), C.byref(b)), "hpgq_dup_debug_kept")
+        return a.value, b.value
+
+    def last_keep_time(self):
+        """Measurement: the keep kernel's us of the last count_device (timing and keeping on)."""
+        a = C.c_float(0)
+        check(lib.hpgq_dup_debug_last_keep_time(self._h, C.byref(a)), "hpgq_dup_debug_last_keep_time")
+        return a.value
+
     def info(self):
         """Tests: (log2 of the slots now, growths since the table was opened)."""
         k, r = C.c_int(0), C.c_int64(0)
@@ -559,6 +604,22 @@ def dup_levels_of(counts):
     lv = DupLevels()
     check(lib.hpgq_dup_levels_of(_ptr(counts), counts.size, C.byref(lv)), "hpgq_dup_levels_of")
     return _levels_dict(lv)
+
+
+def dup_top_of(keys, counts, n, min_count=1):
+    """hpgq_dup_top_of: (keys, counts, total) of the n most frequent pairs with
+    count >= min_count, count descending, ties by key ascending (host only)."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    counts = np.ascontiguousarray(counts, dtype=np.uint64)
+    if keys.ndim != 1 or keys.shape != counts.shape:
+        raise ValueError("keys and counts are u64 vectors of one length")
+    n = min(int(n), keys.size)
+    ok, oc = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+    total = C.c_size_t(0)
+    check(lib.hpgq_dup_top_of(_ptr(keys), _ptr(counts), keys.size, min_count, _ptr(ok), _ptr(oc), n, C.byref(total)),
+          "hpgq_dup_top_of")
+    m = min(n, total.value)
+    return ok[:m], oc[:m], total.value
 
 
 class Signature:

@@ -675,6 +675,42 @@ uint64_t hpgq_dup_level_bound(int level);   /* 0 outside 0 .. HPGQ_DUP_LEVELS - 
 /* the levels of n counts (zeros are no sequence; sums mod 2^64) */
 int  hpgq_dup_levels_of(const uint64_t *counts, size_t n, hpgq_dup_levels_t *out);
 
+/*
+ * stats --overrepresented: the most frequent sequences (build-defined,
+ * DESIGN.md §2.10).  A table in keeping mode copies, after each batch's insert,
+ * the bytes of every counted read of that batch whose key's count in THIS
+ * table is now >= min_count and that has no representative yet, once, into a
+ * device arena of the table.  After hpgq_dup_sync every key whose count here
+ * is >= min_count and that was counted from reads at least once after reaching
+ * it has a representative; hpgq_dup_import makes none.  A representative takes
+ * 16 bytes + its length rounded up to 16 bytes of the arena; one that does not
+ * fit is not kept and hpgq_dup_sync / hpgq_dup_sequence return HPGQ_E_NOMEM
+ * until hpgq_dup_reset (counts, levels, export and top are unaffected).
+ */
+/* Only on an empty table (after open or reset, before any count or import):
+ * otherwise HPGQ_E_STATE.  min_count == 0 turns keeping off and frees the arena.
+ * 1 <= arena_bytes <= 2^40.  Settings survive hpgq_dup_reset, which drops every
+ * representative and empties the arena. */
+int  hpgq_dup_keep_sequences(hpgq_dup_t *d, uint64_t min_count, uint64_t arena_bytes);
+/* The entries with count >= min_count (>= 1), count descending, ties by key
+ * ascending: the first min(cap, *total) of them to keys[] / counts[];
+ * *total = how many qualify (keys == NULL: query only).  Only the qualifying
+ * pairs leave the device.  Synchronises.  Works with keeping off. */
+int  hpgq_dup_top(hpgq_dup_t *d, uint64_t min_count, uint64_t *keys, uint64_t *counts, size_t cap, size_t *total);
+/* The representative of key in THIS table: *len = its length, bytes to buf
+ * (buf == NULL: length query; cap < *len: HPGQ_E_INVALID with *len set).
+ * *len = -1 and HPGQ_OK when the key is absent or has no representative here.
+ * Synchronises.  HPGQ_E_STATE with keeping off. */
+int  hpgq_dup_sequence(hpgq_dup_t *d, uint64_t key, void *buf, size_t cap, int64_t *len);
+/* Tests only: representatives held and the sum of their lengths. */
+int  hpgq_dup_debug_kept(hpgq_dup_t *d, uint64_t *sequences, uint64_t *bytes);
+/* Measurement only: with hpgq_dup_debug_set_timing on and keeping on, the time
+ * of the last launch's keep kernel in microseconds (else HPGQ_E_STATE). */
+int  hpgq_dup_debug_last_keep_time(hpgq_dup_t *d, float *keep_us);
+/* Host only, no device: the same selection over n (key, count) pairs. */
+int  hpgq_dup_top_of(const uint64_t *keys, const uint64_t *counts, size_t n, uint64_t min_count,
+                     uint64_t *out_keys, uint64_t *out_counts, size_t cap, size_t *total);
+
 /* ---------------------------------------------------------------------- */
 /* FASTQ text -> device batch (the parsing half of the producer's          */
 /* fastq_fread_se, src/stats_fastq.c:183, moved onto the GPU)              */

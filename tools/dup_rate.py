@@ -15,7 +15,17 @@ one JSON line per form and writes them all to --out (profiles/dup_rate.json).
 Bytes: fingerprint L + 5 + 8 per read, insert 8 + a 64-byte line per read.  Not
 a test; fails without a GPU.
 
-    python tools/dup_rate.py [--reads 10000000] [--steps 10] [--warmup 3] [--out FILE]
+--keep adds the keep leg: per form and for thresholds 2 and
+100, a table in keeping mode (hpgq_dup_keep_sequences) counted into when
+emptied (the representatives are copied again) and onto itself filled (lookups
+only): keep_kernel's time by its own events beside the fingerprint's and the
+insert's of the same call, the representatives held and the arena bytes they
+take (16 + the length rounded up to 16 each).  Lookup bytes: 8 + a 64-byte line
+per read.  --only-dup leaves out the engine, k-mer and quality-distribution
+calls and the masked leg.  With --keep the default --out is
+profiles/overrep_rate.json.
+
+    python tools/dup_rate.py [--reads 10000000] [--steps 10] [--warmup 3] [--out FILE] [--keep] [--only-dup]
 """
 import argparse
 import ctypes as C
@@ -59,8 +69,13 @@ def main():
     ap.add_argument("--reads", type=int, default=10_000_000)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dup_rate.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--keep", action="store_true", help="add the keep leg (thresholds 2 and 100)")
+    ap.add_argument("--only-dup", action="store_true", help="time hpgq_dup_count_device only")
+    ap.add_argument("--arena", type=int, default=1 << 31, help="--keep: arena bytes of the table")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "overrep_rate.json" if a.keep else "dup_rate.json")
     import torch
     if not torch.cuda.is_available():
         sys.exit("dup_rate: no GPU (rates are measured on the device or not at all)")
@@ -102,16 +117,17 @@ def main():
             batch = H.engine.device_batch(n, seq.data_ptr(), qual.data_ptr(), idx.data_ptr())
             res = {"tool": "dup_rate", "form": form, "reads": n, "read_length": L, "bases": total,
                    "steps": a.steps, "warmup": a.warmup, **box}
-            us, _ = timed(torch, stream, lambda: e.run_device(batch, None, mask.data_ptr(), None), a.warmup, a.steps)
-            res["engine_c2"] = summary(us, 2 * total + 5 * n)
-            res["engine_c2"]["kernels"] = e.kernel_chain
-            km = H.Kmers(L, stream=e.stream)
-            us, _ = timed(torch, stream, lambda: km.count_device(batch, None), a.warmup, a.steps)
-            km.close()
-            res["kmers_all_reads"] = summary(us, total + 4 * n)
-            with H.QualityDist(L, base=33, stream=e.stream) as q:
-                us, _ = timed(torch, stream, lambda: q.count_device(batch, None), a.warmup, a.steps)
-            res["qdist_all_reads"] = summary(us, total + 4 * n)
+            if not a.only_dup:
+                us, _ = timed(torch, stream, lambda: e.run_device(batch, None, mask.data_ptr(), None), a.warmup, a.steps)
+                res["engine_c2"] = summary(us, 2 * total + 5 * n)
+                res["engine_c2"]["kernels"] = e.kernel_chain
+                km = H.Kmers(L, stream=e.stream)
+                us, _ = timed(torch, stream, lambda: km.count_device(batch, None), a.warmup, a.steps)
+                km.close()
+                res["kmers_all_reads"] = summary(us, total + 4 * n)
+                with H.QualityDist(L, base=33, stream=e.stream) as q:
+                    us, _ = timed(torch, stream, lambda: q.count_device(batch, None), a.warmup, a.steps)
+                res["qdist_all_reads"] = summary(us, total + 4 * n)
             with H.Duplication(log2_slots=20, log2_max_slots=30, stream=e.stream) as d:
                 d.count_device(batch, None)      # grows the table to its final size
                 d.sync()
@@ -127,14 +143,34 @@ def main():
                     res[label] = summary(us, fp_bytes + ins_bytes)
                     res[label]["fingerprint_kernel"] = summary([x[0] for x in parts], fp_bytes)
                     res[label]["insert_kernel"] = summary([x[1] for x in parts], ins_bytes)
-                # masked, as `stats --duplication --read-quality-range 20,` runs it
-                d.reset()
-                us, parts = timed(torch, stream, lambda: d.count_device(batch, mask.data_ptr()), a.warmup, a.steps,
-                                  before=d.reset, after=d.last_times)
-                passed = int(mask.sum())
-                res["dup_masked_into_empty_table"] = summary(us, passed * (L + 72) + 13 * n)
-                res["dup_masked_into_empty_table"]["passed_reads"] = passed
-                assert d.levels()["reads"] == passed
+                if not a.only_dup:   # masked, as `stats --duplication --read-quality-range 20,` runs it
+                    d.reset()
+                    us, parts = timed(torch, stream, lambda: d.count_device(batch, mask.data_ptr()), a.warmup, a.steps,
+                                      before=d.reset, after=d.last_times)
+                    passed = int(mask.sum())
+                    res["dup_masked_into_empty_table"] = summary(us, passed * (L + 72) + 13 * n)
+                    res["dup_masked_into_empty_table"]["passed_reads"] = passed
+                    assert d.levels()["reads"] == passed
+            for threshold in (2, 100) if a.keep else ():
+                with H.Duplication(log2_slots=20, log2_max_slots=30, stream=e.stream) as d:
+                    d.keep_sequences(threshold, a.arena)
+                    d.count_device(batch, None)      # grows the table to its final size
+                    d.sync()
+                    d.set_timing(True)
+                    leg = {"arena_bytes": a.arena}
+                    for label, before in (("into_empty_table", d.reset), ("onto_filled_table", None)):
+                        us, parts = timed(torch, stream, lambda: d.count_device(batch, None), a.warmup, a.steps,
+                                          before=before, after=lambda: d.last_times() + (d.last_keep_time(),))
+                        d.sync()                     # (raises if a representative did not fit)
+                        held = d.kept()
+                        leg[label] = summary(us, fp_bytes + ins_bytes + 72 * n)
+                        leg[label]["fingerprint_kernel"] = summary([x[0] for x in parts], fp_bytes)
+                        leg[label]["insert_kernel"] = summary([x[1] for x in parts], ins_bytes)
+                        leg[label]["keep_kernel"] = summary([x[2] for x in parts], 72 * n)
+                        leg[label].update(kept_sequences=held[0], kept_bytes=held[1],
+                                          arena_bytes_used=16 * held[0] + (L + 15) // 16 * 16 * held[0])
+                    assert d.levels()["reads"] == n * (a.warmup + a.steps + 1)
+                    res["keep_at_%d" % threshold] = leg
             print(json.dumps(res), flush=True)
             results.append(res)
             del seq, rows
