@@ -714,7 +714,7 @@ int hpgq_run_device(hpgq_ctx_t *c, const hpgq_batch_t *b, const hpgq_batch_t *b2
   A.seq[0] = b->seq; A.qual[0] = b->quality; A.idx[0] = b->data_indices;
   if (b2) { A.seq[1] = b2->seq; A.qual[1] = b2->quality; A.idx[1] = b2->data_indices; }
   A.mask = mask_out;
-  A.trim = trim_out;
+  A.trim = c->p.edit_on ? trim_out : nullptr;   // (trim_out is edit's output: untouched without it)
   return launch(c, A, true);
 }
 
@@ -884,6 +884,9 @@ static int run_host_slot(hpgq_ctx *c, hpgq_ctx::Slot &sl, const hpgq_batch_t *co
                          const size_t (&bytes)[2], const size_t (&off)[2][3], size_t mask_off, size_t trim_off,
                          bool in_place, uint8_t *mask_out, uint32_t *trim_out) {
   int rc = HPGQ_OK;
+  // trim_out is edit's output: without edit no kernel owes it a store, and the
+  // slot's stale bytes must not reach the caller's array
+  if (!c->p.edit_on) trim_out = nullptr;
   hpgq::EngineArgs A{};
   fill_args(c, A);
   A.num_reads = n;

@@ -221,7 +221,8 @@ void hpgq_close(hpgq_ctx_t *ctx);
  * edit -> filter -> stats kernel asynchronously on the ctx stream and
  * accumulates into the ctx counters.  mask_out[i] = 1 if read (pair) i
  * passed, 0 otherwise; trim_out[i] = trim_start | trim_end << 16 when edit
- * is on (for pairs: mate 1 in trim_out[i], mate 2 in trim_out[num_reads+i]).
+ * is on (for pairs: mate 1 in trim_out[i], mate 2 in trim_out[num_reads+i]);
+ * without edit trim_out is not touched, on this path and on the host path.
  * Either output may be NULL.  For paired ctxs b2 is mate 2 (same num_reads),
  * else it must be NULL.  seq / quality must be readable HPGQ_DEVICE_SLACK bytes
  * past the data end (hpgq_run_host pads its own staging copy).
