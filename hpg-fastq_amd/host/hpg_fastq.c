@@ -38,6 +38,10 @@ int main(int argc, char **argv) {
   cli_options_t *o = cli_parse(cmd, exec_name, argc - 1, argv + 1);
   hpgq_params_t p;
   cli_params(o, &p);
+  if (o->adapters_on && cli_adapters_load(o)) {   /* (one line on stderr; before any GPU work) */
+    cli_free(o);
+    return 1;
+  }
   if (o->print_params) {
     cli_print_params(&p);
     cli_free(o);
@@ -99,6 +103,15 @@ int main(int argc, char **argv) {
     }
     if (f) fclose(f);
   }
+  if (o->adapters_out && r.adapt[0]) {   /* per mate: [nprobes | npos | reads | with_any | first [nprobes][npos]] u64 */
+    FILE *f = fopen(o->adapters_out, "wb");
+    for (int m = 0; m < (p.paired ? 2 : 1); ++m) {
+      const uint64_t head[4] = {(uint64_t)o->adapter_n, (uint64_t)r.adapt_npos[m], r.adapt_reads[m], r.adapt_with_any[m]};
+      const size_t an = (size_t)o->adapter_n * (size_t)r.adapt_npos[m];
+      if (!f || fwrite(head, sizeof(uint64_t), 4, f) != 4 || fwrite(r.adapt[m], sizeof(uint64_t), an, f) != an) rc = 1;
+    }
+    if (f) fclose(f);
+  }
   if (o->cg_out && r.cg_seq) {   /* [table_seq | table_q | word count] u32 */
     const size_t cells = (size_t)1 << (2 * o->k_cg);
     FILE *f = fopen(o->cg_out, "wb");
@@ -126,6 +139,14 @@ int main(int argc, char **argv) {
     if (cli_report_overrep(o, r.overrep_n[m], r.overrep_counts[m], r.overrep_lens[m], r.overrep_seqs[m], r.overrep_reads[m],
                            p.paired ? mate_name[m] : cli_base_name(o->in_filename)))
       rc = 1;
+  /* --adapters: one file per mate, named as that mate's report set */
+  for (int m = 0; cmd == CMD_STATS && m < (p.paired ? 2 : 1); ++m) {
+    const char *names[HPGQ_ADAPT_MAX_PROBES];
+    for (int a = 0; a < o->adapter_n; ++a) names[a] = o->adapter_names[a];
+    if (r.adapt[m] && cli_report_adapt(o, o->adapter_n, names, r.adapt[m], r.adapt_npos[m], r.adapt_reads[m],
+                                       r.adapt_with_any[m], p.paired ? mate_name[m] : cli_base_name(o->in_filename)))
+      rc = 1;
+  }
 
   if (!o->quiet) {
     printf("\n\nRESULTS\n");
@@ -173,6 +194,8 @@ int main(int argc, char **argv) {
   free(r.kmers);
   free(r.qdist[0]);
   free(r.qdist[1]);
+  free(r.adapt[0]);
+  free(r.adapt[1]);
   for (int m = 0; m < 2; ++m) {
     free(r.dup_keys[m]);
     free(r.dup_counts[m]);

@@ -19,6 +19,7 @@
 #include "hpgq.h"
 
 enum { CMD_STATS = 0, CMD_FILTER = 1, CMD_EDIT = 2 };
+#define CLI_ADAPTER_NAME_MAX 64   /* bytes of an adapter's name in --adapter-file */
 
 typedef struct {
   int command;
@@ -40,6 +41,11 @@ typedef struct {
   uint64_t overrep_min_count;   /* K: the merged count a listed sequence has at least */
   int overrep_top;          /* N: sequences listed at most */
   uint64_t overrep_bytes;   /* the arena of every worker's table */
+  int adapters_on;          /* stats --adapters */
+  char *adapter_file;       /* --adapter-file: replaces the default set */
+  int adapter_n;            /* the probe set in order (cli_adapters_load): 1 .. HPGQ_ADAPT_MAX_PROBES */
+  char adapter_names[HPGQ_ADAPT_MAX_PROBES][CLI_ADAPTER_NAME_MAX + 1];
+  char adapter_probes[HPGQ_ADAPT_MAX_PROBES][HPGQ_ADAPT_MAX_LEN + 1];
   /* chaos game (old/main_hpg_fastq_old.c:185-189: --cg | --chaos-game, --k, --gs-filename) */
   int cg_on, k_cg;
   char *gs_filename;
@@ -63,6 +69,7 @@ typedef struct {
   char *cg_out;             /* raw u32 chaos-game tables dump (tests) */
   char *quality_dist_out;   /* raw [npos u64 | hist] per mate dump (tests) */
   char *duplication_out;    /* raw [n u64 | keys ascending | counts] per mate dump (tests) */
+  char *adapters_out;       /* raw [nprobes | npos | reads | with_any | first] u64 per mate dump (tests) */
   int quiet;
   int stream_writer;        /* filter / edit: one writer thread instead of mapped outputs */
   int writer_hook;          /* tests only (--writer-test-hook): hpgq_mapout.h MAPOUT_HOOK_* */
@@ -102,6 +109,11 @@ typedef struct {
   uint64_t *overrep_counts[2], *overrep_lens[2];
   unsigned char **overrep_seqs[2];
   uint64_t overrep_reads[2];
+  /* --adapters: per mate first [adapter_n][adapt_npos] (malloc'd), the counted
+   * reads and those with at least one probe */
+  uint64_t *adapt[2];
+  int adapt_npos[2];
+  uint64_t adapt_reads[2], adapt_with_any[2];
   uint32_t *cg_seq, *cg_q;  /* --cg: table_seq / table_q [dim*dim] (malloc'd) */
   uint32_t cg_words;        /* fq_word_count */
   int cg_exact_calls;       /* chaos-game calls the exact simulation redid */
@@ -130,6 +142,13 @@ int cli_report_dup(const cli_options_t *o, const hpgq_dup_levels_t *lv, const ch
 /* --overrepresented: <base>.overrepresented.data, n sequences in rank order */
 int cli_report_overrep(const cli_options_t *o, size_t n, const uint64_t *counts, const uint64_t *lens,
                        unsigned char *const *seqs, uint64_t reads, const char *base);
+/* --adapters: the probe set into o->adapter_n / _names / _probes, from
+ * --adapter-file or the default set; on a violation one line on stderr and -1.
+ * No device. */
+int cli_adapters_load(cli_options_t *o);
+/* --adapters: <base>.adapter.content.data from one mate's table first[nprobes][npos] */
+int cli_report_adapt(const cli_options_t *o, int nprobes, const char *const *names, const uint64_t *first, int npos,
+                     uint64_t reads, uint64_t with_any, const char *base);
 const char *cli_base_name(const char *path);
 /* the report base names of the two mates: each input's base name, or
  * <base>_1 / <base>_2 for --interleaved (out: 2 x 4096 bytes) */

@@ -9,7 +9,8 @@
  * --counters-out, --kmers-out, --quiet, and stats --quality-dist /
  * --quality-dist-out, --overrepresented and its value flags
  *  and --duplication / --duplication-out
- * (§2.9).  --quality-encoding is accepted by every command
+ * (§2.9), --adapters / --adapter-file / --adapters-out (§2.11).
+ * --quality-encoding is accepted by every command
  * (quirk Q11).
  */
 #define _GNU_SOURCE
@@ -88,6 +89,8 @@ static void usage(const cli_options_t *o) {
     printf("  --overrepresented-min-count=<int>  List the sequences that occur at least this often (default 100)\n");
     printf("  --overrepresented-top=<int>     List at most this many sequences (1-100000, default 20)\n");
     printf("  --overrepresented-bytes=<int>   Device bytes per table for the listed sequences (default 268435456)\n");
+    printf("  --adapters                      Adapter content per read position, exact, over every counted read\n");
+    printf("  --adapter-file=<file>           Probes instead of the default set: lines of name, tab(s), sequence\n");
     printf("  --cg, --chaos-game              Genomic signature (chaos game) tables and images\n");
     printf("  --k=<int>                       Chaos game word size (1-12, default 7)\n");
     printf("  --gs-filename=<file>            Reference genomic signature: difference table and image\n");
@@ -118,6 +121,8 @@ static void usage(const cli_options_t *o) {
     printf("  --quality-dist-out=<file>       Write the raw quality distribution per mate: u64 npos, u64 [npos][256]\n");
   if (o->command == CMD_STATS)
     printf("  --duplication-out=<file>        Write the raw duplication table per mate: u64 n, keys [n], counts [n]\n");
+  if (o->command == CMD_STATS)
+    printf("  --adapters-out=<file>           Write the raw adapter table per mate: u64 nprobes, npos, reads, with_any, [nprobes][npos]\n");
   if (o->command == CMD_STATS)
     printf("  --cg-out=<file>              Write the raw u32 chaos-game tables + word count\n");
   if (o->command != CMD_STATS)
@@ -151,7 +156,8 @@ enum {
   O_THREADS = 1000, O_BATCH, O_QENC, O_KMERS, O_LRANGE, O_QRANGE, O_LLEN, O_LQRANGE, O_RLEN,
   O_RQRANGE, O_MAXN, O_MAXOOQ, O_GPU, O_LMAX, O_CHUNK, O_PRINT, O_COUNTERS, O_QUIET,
   O_KMERSOUT, O_CG, O_KCG, O_GS, O_GPUS, O_CGBATCH, O_CGOUT, O_GPUW, O_STREAMW, O_WHOOK, O_COPYT, O_PFT,
-  O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT, O_DUP, O_DUPOUT, O_OVER, O_OVERMIN, O_OVERTOP, O_OVERBYTES
+  O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT, O_DUP, O_DUPOUT, O_OVER, O_OVERMIN, O_OVERTOP, O_OVERBYTES,
+  O_ADAPT, O_ADAPTFILE, O_ADAPTOUT
 };
 
 /* a whole-string decimal in [lo, hi] (u64), else the usage error */
@@ -189,6 +195,7 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   o->overrep_top = 20;
   o->overrep_bytes = (uint64_t)1 << 28;
   int overrep_values = 0;   /* a value flag of --overrepresented was given */
+  int adapter_values = 0;   /* --adapter-file or --adapters-out was given */
   static const struct option longopts[] = {
       {"help", no_argument, 0, 'h'},
       {"fastq-file", required_argument, 0, 'f'},
@@ -232,6 +239,9 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
       {"overrepresented-min-count", required_argument, 0, O_OVERMIN},
       {"overrepresented-top", required_argument, 0, O_OVERTOP},
       {"overrepresented-bytes", required_argument, 0, O_OVERBYTES},
+      {"adapters", no_argument, 0, O_ADAPT},
+      {"adapter-file", required_argument, 0, O_ADAPTFILE},
+      {"adapters-out", required_argument, 0, O_ADAPTOUT},
       {"quiet", no_argument, 0, O_QUIET},
       {"stream-writer", no_argument, 0, O_STREAMW},
       {"writer-test-hook", required_argument, 0, O_WHOOK},
@@ -289,6 +299,24 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
         if (c == O_OVERTOP) o->overrep_top = count_arg(o, "overrepresented-top", optarg, 1, 100000);
         if (c == O_OVERBYTES) o->overrep_bytes = u64_arg(o, "overrepresented-bytes", optarg, 1, (uint64_t)1 << 40);
         break;
+      case O_ADAPT:
+      case O_ADAPTFILE:
+      case O_ADAPTOUT:
+        if (command != CMD_STATS) {   /* one line, before anything is opened or written */
+          fprintf(stderr, "hpg-fastq: --adapters is an option of the stats command, not of %s\n", o->command_name);
+          exit(1);
+        }
+        if (c == O_ADAPT) o->adapters_on = 1;
+        else adapter_values = 1;
+        if (c == O_ADAPTFILE) {
+          free(o->adapter_file);
+          o->adapter_file = strdup(optarg);
+        }
+        if (c == O_ADAPTOUT) {
+          free(o->adapters_out);
+          o->adapters_out = strdup(optarg);
+        }
+        break;
       case O_CG:
         if (command != CMD_STATS) usage(o);
         o->cg_on = 1;
@@ -342,6 +370,10 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   }
   if (overrep_values && !o->overrep_on) {
     printf("\nError: --overrepresented-min-count, -top and -bytes need --overrepresented\n");
+    usage(o);
+  }
+  if (adapter_values && !o->adapters_on) {
+    printf("\nError: --adapter-file and --adapters-out need --adapters\n");
     usage(o);
   }
   if (fq1) o->in_filename = fq1;
@@ -462,6 +494,8 @@ void cli_display(const cli_options_t *o) {
   if (o->overrep_on)
     printf("\tOverrepresented      : top %d with count >= %lu (--overrepresented)\n", o->overrep_top,
            (unsigned long)o->overrep_min_count);
+  if (o->adapters_on)
+    printf("\tAdapter content      : %d probes, first occurrence per read (--adapters)\n", o->adapter_n);
   printf("\n%s options\n", o->command == CMD_EDIT ? "Edit and filter" : "Filter");
   int shown = 0;
   if (o->read_length_range) printf("\tRead length range   : %s\n", o->read_length_range), shown++;
@@ -571,6 +605,8 @@ void cli_free(cli_options_t *o) {
   free(o->cg_out);
   free(o->quality_dist_out);
   free(o->duplication_out);
+  free(o->adapter_file);
+  free(o->adapters_out);
   free(o->gs_filename);
   free(o);
 }

@@ -812,6 +812,7 @@ typedef struct {
   hpgq_kmers_t *km;
   hpgq_qdist_t *qd[2];    /* --quality-dist: one table per mate, on the ctx stream */
   hpgq_dup_t *dp[2];      /* --duplication: one hash table per mate, on the ctx stream */
+  hpgq_adapt_t *ad[2];    /* --adapters: one table per mate, on the ctx stream */
   hpgq_cgr_t *cg;
   uint8_t *d_mask;
   uint32_t *d_trim;
@@ -834,6 +835,12 @@ static int worker_open(worker_t *W) {
    * input): lmax rows to start with, the window of on-chip values from phred */
   for (int m = 0; m < W->P->nmates && rc == 0 && o->quality_dist_on; ++m)
     rc = hpgq_qdist_open(&W->qd[m], W->device, W->p->lmax, W->p->phred, hpgq_stream(W->ctx));
+  /* --adapters counts the same reads, per mate: lmax rows to start with */
+  for (int m = 0; m < W->P->nmates && rc == 0 && o->adapters_on; ++m) {
+    const char *probes[HPGQ_ADAPT_MAX_PROBES];
+    for (int a = 0; a < o->adapter_n; ++a) probes[a] = o->adapter_probes[a];
+    rc = hpgq_adapt_open(&W->ad[m], W->device, probes, o->adapter_n, W->p->lmax, hpgq_stream(W->ctx));
+  }
   /* --duplication counts the same reads again, per mate, by their sequence;
    * --overrepresented needs the same tables, keeping the bytes of the sequences
    * that reach ceil(K / workers) in one of them: a sequence with K or more in
@@ -859,6 +866,8 @@ static void worker_close(worker_t *W) {
   hpgq_kmers_close(W->km);
   hpgq_qdist_close(W->qd[0]);
   hpgq_qdist_close(W->qd[1]);
+  hpgq_adapt_close(W->ad[0]);
+  hpgq_adapt_close(W->ad[1]);
   hpgq_dup_close(W->dp[0]);
   hpgq_dup_close(W->dp[1]);
   hpgq_cgr_close(W->cg);
@@ -922,7 +931,7 @@ static int worker_chunk(worker_t *W, slot_t *s) {
   const int nm = P->nmates, ns = P->nsides;
   const int writes = o->command != CMD_STATS;
   const int edit = o->command == CMD_EDIT;
-  const int need_mask = writes || ((W->km || W->cg || W->qd[0] || W->dp[0]) && o->filter_on);
+  const int need_mask = writes || ((W->km || W->cg || W->qd[0] || W->dp[0] || W->ad[0]) && o->filter_on);
   const char *const text[2] = {s->buf, s->buf2};
   const size_t use[2] = {s->use, s->use2};
   hpgq_batch_t b[2];
@@ -966,12 +975,15 @@ static int worker_chunk(worker_t *W, slot_t *s) {
     rc = hpgq_reserve_length(W->ctx, ml);
     if (rc == 0 && W->km) rc = hpgq_kmers_reserve_length(W->km, ml);
     for (int m = 0; m < nm && rc == 0 && W->qd[m]; ++m) rc = hpgq_qdist_reserve_length(W->qd[m], ml);
+    for (int m = 0; m < nm && rc == 0 && W->ad[m]; ++m) rc = hpgq_adapt_reserve_length(W->ad[m], ml);
   }
   if (rc == 0)
     rc = hpgq_run_device(W->ctx, &b[0], nm == 2 ? &b[1] : NULL, need_mask ? W->d_mask : NULL, edit ? W->d_trim : NULL);
   if (rc == 0 && W->km) rc = hpgq_kmers_count_device(W->km, &b[0], o->filter_on ? W->d_mask : NULL);
   for (int m = 0; m < nm && rc == 0 && W->qd[m]; ++m)   /* (paired: the pair mask for both mates) */
     rc = hpgq_qdist_count_device(W->qd[m], &b[m], o->filter_on ? W->d_mask : NULL);
+  for (int m = 0; m < nm && rc == 0 && W->ad[m]; ++m)   /* (the same reads, the same mask) */
+    rc = hpgq_adapt_count_device(W->ad[m], &b[m], o->filter_on ? W->d_mask : NULL);
   for (int m = 0; m < nm && rc == 0 && W->dp[m]; ++m)   /* (the same reads, the same mask) */
     rc = hpgq_dup_count_device(W->dp[m], &b[m], o->filter_on ? W->d_mask : NULL);
   if (rc == 0 && writes) {
@@ -1250,6 +1262,31 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
       int32_t pw = 0;
       rc = hpgq_qdist_read(W[w].qd[m], part, (size_t)HPGQ_QDIST_VALUES * np, &pw);
       if (rc == 0) rc = hpgq_qdist_add(res->qdist[m], np, part, pw);
+    }
+    free(part);
+  }
+  /* --adapters: per mate, the workers' tables added at the longest worker's
+   * positions (hpgq_adapt_add), and the two scalars added */
+  for (int m = 0; m < nm && rc == 0 && o->adapters_on; ++m) {
+    const size_t na = (size_t)o->adapter_n;
+    int32_t np = 0;
+    hpgq_adapt_info_t info;
+    for (int w = 0; w < G && rc == 0; ++w) {
+      rc = hpgq_adapt_read(W[w].ad[m], NULL, 0, &info);
+      if (rc == 0 && info.npos > np) np = info.npos;
+    }
+    res->adapt_npos[m] = np;
+    res->adapt[m] = rc == 0 ? calloc(na * (size_t)np + 1, sizeof(uint64_t)) : NULL;
+    if (rc == 0 && !res->adapt[m]) rc = HPGQ_E_NOMEM;
+    uint64_t *part = rc == 0 ? calloc(na * (size_t)np + 1, sizeof(uint64_t)) : NULL;
+    if (rc == 0 && !part) rc = HPGQ_E_NOMEM;
+    for (int w = 0; w < G && rc == 0; ++w) {
+      rc = hpgq_adapt_read(W[w].ad[m], part, na * (size_t)np, &info);
+      if (rc == 0) rc = hpgq_adapt_add(res->adapt[m], np, part, info.npos, (int)na);
+      if (rc == 0) {
+        res->adapt_reads[m] += info.reads;
+        res->adapt_with_any[m] += info.with_any;
+      }
     }
     free(part);
   }

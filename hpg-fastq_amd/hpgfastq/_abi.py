@@ -33,6 +33,7 @@ E_READ_TOO_LONG = -4
 E_INVALID, E_NOMEM, E_STATE = -1, -3, -7
 QDIST_VALUES = 256
 DUP_LEVELS = 16
+ADAPT_MAX_PROBES, ADAPT_MIN_LEN, ADAPT_MAX_LEN = 32, 8, 32
 
 
 class HpgqError(RuntimeError):
@@ -93,6 +94,10 @@ class QdistRow(C.Structure):
 class DupLevels(C.Structure):
     _fields_ = [("reads", C.c_uint64), ("distinct", C.c_uint64), ("max_count", C.c_uint64),
                 ("distinct_at", C.c_uint64 * DUP_LEVELS), ("reads_at", C.c_uint64 * DUP_LEVELS)]
+
+
+class AdaptInfo(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("with_any", C.c_uint64), ("nprobes", C.c_int32), ("npos", C.c_int32)]
 
 
 class GsInfo(C.Structure):
@@ -219,6 +224,17 @@ _SIGS = [
     ("hpgq_dup_debug_last_keep_time", C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     ("hpgq_dup_top_of", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t,
                                   C.POINTER(C.c_size_t)]),
+    ("hpgq_adapt_open", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_void_p]),
+    ("hpgq_adapt_close", None, [C.c_void_p]),
+    ("hpgq_adapt_reserve_length", C.c_int, [C.c_void_p, C.c_int64]),
+    ("hpgq_adapt_count_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p]),
+    ("hpgq_adapt_sync", C.c_int, [C.c_void_p]),
+    ("hpgq_adapt_reset", C.c_int, [C.c_void_p]),
+    ("hpgq_adapt_read", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AdaptInfo)]),
+    ("hpgq_adapt_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
+    ("hpgq_adapt_add", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    ("hpgq_adapt_find", C.c_int64, [C.c_char_p, C.c_size_t, C.c_char_p]),
+    ("hpgq_adapt_default", C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
     ("hpgq_synth_length", C.c_int32, [C.POINTER(Synth), C.c_int64]),
     ("hpgq_synth_indices_host", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p]),
     ("hpgq_synth_device", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p,

@@ -9,8 +9,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, counters_len, CGR_ALL_READS,
-                   ROUTES, E_PAIRING, QDIST_VALUES, DUP_LEVELS)
+from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, AdaptInfo, counters_len,
+                   CGR_ALL_READS, ROUTES, E_PAIRING, QDIST_VALUES, DUP_LEVELS, HpgqError)
 
 # Kernel route for new Engines (tests / A/B: a key of ROUTES, or None for the
 # library's automatic chain).  Applied through hpgq_debug_set_route: the
@@ -448,6 +448,98 @@ def qdist_quantiles(hist, phred):
         r = rows[p]
         out[p, 1:] = (r.min, r.p10, r.q1, r.median, r.q3, r.p90, r.max)
         out.view(np.uint64)[p, 0] = r.count   # (a count of 2^63 or more: its two's complement)
+    return out
+
+
+class AdapterContent:
+    """hpgq_adapt: `stats --adapters`, per probe the counted reads whose first
+    occurrence of it starts at each read position.  `probes`:
+    byte strings of 8 .. 32 A C G T, at most 32 of them (None: the default
+    set).  `rows` positions are reserved (reserve_length grows them)."""
+
+    def __init__(self, probes=None, rows=1024, device=0, stream=None):
+        self._h = None
+        if probes is None:
+            probes = [p for _, p in adapt_defaults()]
+        self.probes = [p.encode() if isinstance(p, str) else bytes(p) for p in probes]
+        arr = (C.c_char_p * max(len(self.probes), 1))(*self.probes)
+        h = C.c_void_p()
+        check(lib.hpgq_adapt_open(C.byref(h), device, arr, len(self.probes), rows, stream), "hpgq_adapt_open")
+        self._h = h
+
+    def close(self):
+        if self._h:
+            lib.hpgq_adapt_close(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def count_device(self, batch, mask_ptr=None):
+        check(lib.hpgq_adapt_count_device(self._h, C.byref(batch), mask_ptr), "hpgq_adapt_count_device")
+
+    def reserve_length(self, max_len):
+        check(lib.hpgq_adapt_reserve_length(self._h, int(max_len)), "hpgq_adapt_reserve_length")
+
+    def sync(self):
+        """HpgqError -4 after a counted read longer than the rows, until reset()."""
+        check(lib.hpgq_adapt_sync(self._h), "hpgq_adapt_sync")
+
+    def reset(self):
+        check(lib.hpgq_adapt_reset(self._h), "hpgq_adapt_reset")
+
+    def set_max_workgroups(self, max_wg):
+        check(lib.hpgq_adapt_debug_set_max_workgroups(self._h, max_wg), "hpgq_adapt_debug_set_max_workgroups")
+
+    def table(self):
+        """(first u64 [nprobes, npos], dict(reads, with_any, nprobes, npos)); npos =
+        the longest counted read (synchronises)."""
+        info = AdaptInfo()
+        check(lib.hpgq_adapt_read(self._h, None, 0, C.byref(info)), "hpgq_adapt_read")
+        out = np.zeros((info.nprobes, info.npos), dtype=np.uint64)
+        check(lib.hpgq_adapt_read(self._h, _ptr(out), out.size, C.byref(info)), "hpgq_adapt_read")
+        return out, dict(reads=int(info.reads), with_any=int(info.with_any), nprobes=int(info.nprobes),
+                         npos=int(info.npos))
+
+
+def adapt_add(dst, src):
+    """hpgq_adapt_add: dst[:, :src.shape[1]] += src, in place (both C-contiguous
+    (nprobes, npos) u64 arrays, dst with at least src's positions)."""
+    if not (isinstance(dst, np.ndarray) and dst.dtype == np.uint64 and dst.flags.c_contiguous and dst.ndim == 2):
+        raise ValueError("dst must be a C-contiguous (nprobes, npos) u64 array")
+    src = np.ascontiguousarray(src, dtype=np.uint64)
+    if src.ndim != 2 or src.shape[0] != dst.shape[0]:
+        raise ValueError("src must be (nprobes, npos) u64 with dst's probes")
+    check(lib.hpgq_adapt_add(_ptr(dst), dst.shape[1], _ptr(src), src.shape[1], dst.shape[0]), "hpgq_adapt_add")
+    return dst
+
+
+def adapt_find(s, probe):
+    """hpgq_adapt_find: the lowest position of probe in the bytes s, -1 if none
+    (HpgqError -1 for a probe that breaks the rules)."""
+    s = bytes(s)
+    r = lib.hpgq_adapt_find(s, len(s), probe.encode() if isinstance(probe, str) else bytes(probe))
+    if r == -2:
+        raise HpgqError(-1, "hpgq_adapt_find")
+    return int(r)
+
+
+def adapt_defaults():
+    """hpgq_adapt_default: [(name, probe)] of the default set, both bytes."""
+    out = []
+    for i in range(lib.hpgq_adapt_default(-1, None, None)):
+        name, probe = C.c_char_p(), C.c_char_p()
+        lib.hpgq_adapt_default(i, C.byref(name), C.byref(probe))
+        out.append((name.value, probe.value))
     return out
 
 

@@ -64,7 +64,7 @@ extern "C" {
 #define HPGQ_E_INVALID         (-1)   /* bad argument / parameter            */
 #define HPGQ_E_HIP             (-2)   /* HIP runtime error                    */
 #define HPGQ_E_NOMEM           (-3)   /* device or host allocation failed     */
-#define HPGQ_E_READ_TOO_LONG   (-4)   /* hpgq_qdist_sync / _read only: a counted read
+#define HPGQ_E_READ_TOO_LONG   (-4)   /* hpgq_qdist_ / hpgq_adapt_sync / _read only: a counted read
                                          longer than the reserved rows (the engine
                                          and k-mers merge reads of any length)  */
 #define HPGQ_E_NO_DEVICE       (-5)   /* no HIP device                        */
@@ -711,6 +711,64 @@ int  hpgq_dup_debug_last_keep_time(hpgq_dup_t *d, float *keep_us);
 /* Host only, no device: the same selection over n (key, count) pairs. */
 int  hpgq_dup_top_of(const uint64_t *keys, const uint64_t *counts, size_t n, uint64_t min_count,
                      uint64_t *out_keys, uint64_t *out_counts, size_t cap, size_t *total);
+
+/* ---------------------------------------------------------------------- */
+/* stats --adapters: adapter content per read position                      */
+/* ---------------------------------------------------------------------- */
+
+/*
+ * Build-defined.  A probe is a string of HPGQ_ADAPT_MIN_LEN
+ * .. HPGQ_ADAPT_MAX_LEN bytes, each one of A C G T (upper case); a set holds 1
+ * .. HPGQ_ADAPT_MAX_PROBES of them (identical probes give identical rows).
+ * Probe a occurs at position j of a read of n bytes iff j + K <= n and the
+ * read's bytes [j, j + K) equal the probe's: bytes.find, nothing else; N,
+ * lower case and every other byte value never match, and a window never
+ * reaches past the read's last byte.  For every counted read and every probe
+ * that occurs in it, first[a][p] += 1 at the LOWEST such position p (u64).
+ * reads: the counted reads; with_any: those in which at least one probe
+ * occurs; npos: the longest counted read.
+ *
+ * The table has `rows` positions.  A counted read longer than the rows makes
+ * hpgq_adapt_sync and hpgq_adapt_read return HPGQ_E_READ_TOO_LONG until
+ * hpgq_adapt_reset (the table's contents are unspecified until then): call
+ * hpgq_adapt_reserve_length first.  There is no second pass and no tail.
+ */
+typedef struct hpgq_adapt hpgq_adapt_t;
+#define HPGQ_ADAPT_MAX_PROBES 32
+#define HPGQ_ADAPT_MIN_LEN 8
+#define HPGQ_ADAPT_MAX_LEN 32
+typedef struct hpgq_adapt_info { uint64_t reads, with_any; int32_t nprobes, npos; } hpgq_adapt_info_t;
+
+/* probes: nprobes NUL-terminated strings, copied; rows >= 1; stream: as
+ * hpgq_kmers_open.  HPGQ_E_INVALID before any device call. */
+int  hpgq_adapt_open(hpgq_adapt_t **ad, int device, const char *const *probes, int nprobes, int rows, void *stream);
+void hpgq_adapt_close(hpgq_adapt_t *ad);
+/* grow the table to >= max_len rows (counts kept; async on the stream; never shrinks) */
+int  hpgq_adapt_reserve_length(hpgq_adapt_t *ad, int64_t max_len);
+/* Count a DEVICE batch, async; only `seq` and `data_indices` are read (seq
+ * readable HPGQ_DEVICE_SLACK bytes past the data end, any alignment, absolute
+ * offsets); reads of any length, 0 included, and an empty batch.  mask (device,
+ * may be NULL): only reads with mask[i] == 1 are counted. */
+int  hpgq_adapt_count_device(hpgq_adapt_t *ad, const hpgq_batch_t *b, const uint8_t *mask);
+int  hpgq_adapt_sync(hpgq_adapt_t *ad);
+/* zero the table, both scalars, the longest read and the too-long state
+ * (async); the probes and the rows stay */
+int  hpgq_adapt_reset(hpgq_adapt_t *ad);
+/* first[a * npos + p]; n >= nprobes * npos (first == NULL: size query, info
+ * only; info may be NULL if first is not).  Synchronises. */
+int  hpgq_adapt_read(hpgq_adapt_t *ad, uint64_t *first, size_t n, hpgq_adapt_info_t *info);
+/* Tests only: at most max_wg workgroups (0, the default: no limit). */
+int  hpgq_adapt_debug_set_max_workgroups(hpgq_adapt_t *ad, int max_wg);
+/* Host only, no device (csrc/hpgq_adapt_post.cpp).
+ * dst[a][p] += src[a][p] for p < npos_src, dst's rows npos_dst long and src's
+ * npos_src: merges shards' tables (HPGQ_E_INVALID if npos_src > npos_dst). */
+int  hpgq_adapt_add(uint64_t *dst, int npos_dst, const uint64_t *src, int npos_src, int nprobes);
+/* the lowest position at which probe occurs in s[0, n), -1 if none, -2 for a
+ * probe that breaks the rules above */
+int64_t hpgq_adapt_find(const void *s, size_t n, const char *probe);
+/* the number of default probes (6); for 0 <= i < 6 *name and *probe (either
+ * may be NULL) are set to static strings */
+int  hpgq_adapt_default(int i, const char **name, const char **probe);
 
 /* ---------------------------------------------------------------------- */
 /* FASTQ text -> device batch (the parsing half of the producer's          */
