@@ -6,13 +6,13 @@
 // One kernel.  It reads the sequence bytes, the offsets and the mask and
 // nothing else (L + 4 + 1 bytes per read).  Read-major: a wave takes kR = 16
 // consecutive reads per step (one coalesced load of their 17 offsets and 16
-// mask bytes, as hpgq_qdist.hip does) and scans them one after the other, four
+// mask bytes: hpgq_reads.h) and scans them one after the other, four
 // reads' first loads in flight, because "first occurrence" is a property of
 // the whole read: the found-mask of a read (one bit per probe, wave-uniform)
 // lives across the steps of a long read.
 //
 // A step: lane l takes the read's bytes p0 + 4l .. p0 + 4l + 3 (one 8-byte
-// dword-aligned load and v_alignbyte, as in hpgq_qdist.hip), zeroes those past
+// dword-aligned load, hpgq_reads.h, and v_alignbyte), zeroes those past
 // the read's end, and packs them, four bytes at once, into four 2-bit base
 // codes ((b >> 1) & 3: A 0, C 1, T 2, G 3) and four validity bits: the byte is
 // exactly the one base with its code.  2-bit codes alias (a, N and 250 other
@@ -53,7 +53,8 @@
 // with_any, the longest counted read and the counted reads longer than the
 // rows take one add per workgroup.  A counted read longer than the rows is not
 // scanned.
-#include "hpgq_common.h"
+#include "hpgq_accum.h"
+#include "hpgq_reads.h"
 
 #include <algorithm>
 #include <climits>
@@ -71,8 +72,7 @@ constexpr int kR = 16;      // reads per wave step
 constexpr int kPre = 4;     // of them with their first load in flight
 constexpr int kGroup = kWaves * kR;   // reads per workgroup step
 constexpr int kNarrowMax = 13;        // longest probe of the 32-bit window: 16 bases less the 3 a start may skip
-constexpr uint32_t kNone = 0xFFFFFFF0u;   // an offset past every descriptor: reads 0, no traffic
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
+using reads::v2u;
 constexpr int kBitmapWords = 65536 / 32;   // one bit per 8-base prefix (16 code bits)
 static_assert(kR % kPre == 0, "the reads of a wave step go in blocks of kPre");
 static_assert(kMaxProbes == 32, "the found-mask is one 32-bit word");
@@ -91,14 +91,6 @@ __device__ __forceinline__ uint32_t pull(uint32_t v, int lane, int d) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + d) & 63) * 4, (int)v);
 }
 
-// the step's 8 bytes of lane `lane`: dwords l and l + 1 from the dword at or
-// below byte st (from the descriptor's base); rem: the read's bytes from st on.
-// The last byte is at most 6 past the read's end: inside the slack.
-__device__ __forceinline__ v2u load_step(const __amdgpu_buffer_rsrc_t rq, uint32_t st, int rem, int lane) {
-  const bool need = 4 * lane < rem;
-  return __builtin_amdgcn_raw_buffer_load_b64(rq, need ? (st & ~3u) + 4u * (uint32_t)lane : kNone, 0, 0);
-}
-
 // One counted read of len <= rows bytes at st0 (from the descriptor's base);
 // w0: its first step's load.  Everything but the lane's bytes is wave-uniform.
 template <bool WIDE>
@@ -112,7 +104,7 @@ __device__ __forceinline__ uint32_t scan_read(const __amdgpu_buffer_rsrc_t rq, c
   for (int p0 = 0; p0 + pr.kmin <= len; p0 += S) {
     const int rem = len - p0;
     const uint32_t st = st0 + (uint32_t)p0;
-    const v2u w = p0 == 0 ? w0 : load_step(rq, st, rem, lane);
+    const v2u w = p0 == 0 ? w0 : reads::lane_load8(rq, st, rem, lane);
     // positions p0 + 4 lane + [0, 4); the bytes past the read's end become 0, which is no base
     const int nb = rem - 4 * lane;
     const uint32_t raw = __builtin_amdgcn_alignbyte(w[1], w[0], st & 3u);
@@ -218,17 +210,7 @@ __global__ void __launch_bounds__(kWG) adapt_kernel(const char *seq, const int32
     atomicOr(&bm[ix8 >> 5], 1u << (ix8 & 31u));
   }
   __syncthreads();
-  // the sequence bytes through a descriptor whose base is dword-aligned: the
-  // bytes of the first dword before `seq`, the bytes between reads and
-  // HPGQ_DEVICE_SLACK past the end are readable, and anything further reads 0
-  const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(seq) & 3u);
-  const int32_t data_end = __builtin_amdgcn_readfirstlane(idx[n]);
-  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)(seq - shift), (short)0, (uint32_t)data_end + shift + HPGQ_DEVICE_SLACK, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)idx, (short)0, (uint32_t)((n + 1) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)mask, (short)0, MASK ? (uint32_t)n : 0u, 0x00020000);
+  const reads::Batch rd = reads::open<MASK>(seq, idx, n, mask);
   const int64_t ngroups = (n + kGroup - 1) / kGroup;
   // lane a holds probe a: its code's halves and its length
   const int pa = lane < pr.n ? lane : 0;
@@ -239,14 +221,9 @@ __global__ void __launch_bounds__(kWG) adapt_kernel(const char *seq, const int32
   for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
     const int64_t rb = g * kGroup + wave * kR;
     if (rb >= n) continue;
-    // lane l: offset of read rb + l (17 of them) and its mask byte; past the
-    // batch both read 0
-    const int64_t r = rb + lane;
-    const int32_t ix = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(
-        ri, r <= n && lane <= kR ? (uint32_t)r * 4u : kNone, 0, 0);
-    const bool on = r < n && lane < kR;
-    const uint32_t mk = MASK ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rm, on ? (uint32_t)r : kNone, 0, 0)
-                             : (on ? 1u : 0u);
+    int32_t ix;
+    uint32_t mk;
+    reads::step_reads<kR, MASK>(rd, rb, n, lane, ix, mk);
     // read i of the step: its first byte from the descriptor's base, its
     // length, and whether it is scanned (counted, inside the rows, long enough)
     auto first_load = [&](int i) {
@@ -254,7 +231,7 @@ __global__ void __launch_bounds__(kWG) adapt_kernel(const char *seq, const int32
       const int32_t len = __builtin_amdgcn_readlane(ix, i + 1) - a;
       const bool cnt = (uint32_t)__builtin_amdgcn_readlane((int)mk, i) == 1u;
       const bool scan = cnt && len <= rows && len >= pr.kmin;
-      return load_step(rq, (uint32_t)a + shift, scan ? len : 0, lane);
+      return reads::lane_load8(rd.bytes, (uint32_t)a + rd.shift, scan ? len : 0, lane);
     };
     v2u wq[kPre];
 #pragma unroll
@@ -275,7 +252,7 @@ __global__ void __launch_bounds__(kWG) adapt_kernel(const char *seq, const int32
           ++clipped;
           continue;
         }
-        if (scan_read<WIDE>(rq, pr, lane, (uint32_t)a + shift, len, w, pc_lo, pc_hi, pk, t, bm, first)) ++nany;
+        if (scan_read<WIDE>(rd.bytes, pr, lane, (uint32_t)a + rd.shift, len, w, pc_lo, pc_hi, pk, t, bm, first)) ++nany;
       }
     }
   }
@@ -311,35 +288,14 @@ __global__ void __launch_bounds__(kWG) adapt_kernel(const char *seq, const int32
 }  // namespace adapt
 }  // namespace hpgq
 
-struct hpgq_adapt {
-  int device = 0;
-  int64_t rows = 0;
+// the table: first[rows][32]; the scalars: [reads, with_any]
+struct hpgq_adapt : hpgq::accum::Positions {
   hpgq::adapt::Probes pr;
   bool wide = false;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  unsigned long long *d_first = nullptr;   // [rows][32]: position-major, so that growing appends rows
-  unsigned long long *d_scal = nullptr;    // [reads, with_any]
-  uint32_t *d_flags = nullptr;             // [longest counted read, counted reads longer than the rows]
-  unsigned long long *h_scal = nullptr;    // pinned: the two scalars, then the two flags
-  int cus = 0, max_wg = 0;
-  std::vector<void *> retired;             // tables replaced by a larger one: freed once the stream is idle
 };
 
 namespace {
 constexpr size_t kRowBytes = (size_t)HPGQ_ADAPT_MAX_PROBES * 8;
-
-uint32_t *h_flags(hpgq_adapt *q) { return reinterpret_cast<uint32_t *>(q->h_scal + 2); }
-
-// wait for the stream, fetch the scalars and the flags, free the replaced tables
-int a_settle(hpgq_adapt *q) {
-  HPGQ_HIP_TRY(hipMemcpyAsync(q->h_scal, q->d_scal, 16, hipMemcpyDeviceToHost, q->stream));
-  HPGQ_HIP_TRY(hipMemcpyAsync(h_flags(q), q->d_flags, 8, hipMemcpyDeviceToHost, q->stream));
-  HPGQ_HIP_TRY(hipStreamSynchronize(q->stream));
-  for (void *p : q->retired) (void)hipFree(p);
-  q->retired.clear();
-  return h_flags(q)[1] ? HPGQ_E_READ_TOO_LONG : HPGQ_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -361,37 +317,14 @@ int hpgq_adapt_open(hpgq_adapt_t **ad, int device, const char *const *probes, in
     pr.kmin = std::min(pr.kmin, k);
     kmax = std::max(kmax, k);
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return HPGQ_E_NO_DEVICE;
-  if (device < 0 || device >= ndev) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(device));
+  int rc = hpgq::accum::use_device(device);
+  if (rc) return rc;
   hpgq_adapt *q = new hpgq_adapt;
-  q->device = device;
-  q->rows = rows;
   q->pr = pr;
   q->wide = kmax > hpgq::adapt::kNarrowMax;
-  if (stream) {
-    q->stream = (hipStream_t)stream;
-  } else {
-    if (hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete q;
-      return HPGQ_E_HIP;
-    }
-    q->own_stream = true;
-  }
-  if (hipMalloc(&q->d_first, (size_t)rows * kRowBytes) != hipSuccess || hipMalloc(&q->d_scal, 16) != hipSuccess ||
-      hipMalloc(&q->d_flags, 8) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void **>(&q->h_scal), 24, hipHostMallocDefault) != hipSuccess) {
+  if ((rc = q->open(device, stream, rows, kRowBytes, 2)) != HPGQ_OK) {
     hpgq_adapt_close(q);
-    return HPGQ_E_NOMEM;
-  }
-  std::memset(q->h_scal, 0, 24);
-  if (hipMemsetAsync(q->d_first, 0, (size_t)rows * kRowBytes, q->stream) != hipSuccess ||
-      hipMemsetAsync(q->d_scal, 0, 16, q->stream) != hipSuccess ||
-      hipMemsetAsync(q->d_flags, 0, 8, q->stream) != hipSuccess ||
-      hipDeviceGetAttribute(&q->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
-    hpgq_adapt_close(q);
-    return HPGQ_E_HIP;
+    return rc;
   }
   *ad = q;
   return HPGQ_OK;
@@ -399,36 +332,12 @@ int hpgq_adapt_open(hpgq_adapt_t **ad, int device, const char *const *probes, in
 
 void hpgq_adapt_close(hpgq_adapt_t *q) {
   if (!q) return;
-  (void)hipSetDevice(q->device);
-  if (q->stream) (void)hipStreamSynchronize(q->stream);
-  for (void *p : q->retired) (void)hipFree(p);
-  (void)hipFree(q->d_first);
-  (void)hipFree(q->d_scal);
-  (void)hipFree(q->d_flags);
-  if (q->h_scal) (void)hipHostFree(q->h_scal);
-  if (q->own_stream) (void)hipStreamDestroy(q->stream);
+  q->close();
   delete q;
 }
 
 int hpgq_adapt_reserve_length(hpgq_adapt_t *q, int64_t max_len) {
-  if (!q || max_len < 0 || max_len > INT32_MAX) return HPGQ_E_INVALID;
-  if (max_len <= q->rows) return HPGQ_OK;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  // (half as much again at least: a file whose units grow slowly reallocates rarely)
-  const int64_t nr = std::min<int64_t>(std::max<int64_t>(max_len, q->rows + q->rows / 2), INT32_MAX);
-  unsigned long long *d = nullptr;
-  if (hipMalloc(&d, (size_t)nr * kRowBytes) != hipSuccess) return HPGQ_E_NOMEM;
-  const size_t old = (size_t)q->rows * kRowBytes;
-  if (hipMemcpyAsync(d, q->d_first, old, hipMemcpyDeviceToDevice, q->stream) != hipSuccess ||
-      hipMemsetAsync(reinterpret_cast<char *>(d) + old, 0, (size_t)nr * kRowBytes - old, q->stream) != hipSuccess) {
-    (void)hipStreamSynchronize(q->stream);
-    (void)hipFree(d);
-    return HPGQ_E_HIP;
-  }
-  q->retired.push_back(q->d_first);   // the copy above still reads it
-  q->d_first = d;
-  q->rows = nr;
-  return HPGQ_OK;
+  return q ? q->reserve_length(max_len) : HPGQ_E_INVALID;
 }
 
 int hpgq_adapt_count_device(hpgq_adapt_t *q, const hpgq_batch_t *b, const uint8_t *mask) {
@@ -437,49 +346,29 @@ int hpgq_adapt_count_device(hpgq_adapt_t *q, const hpgq_batch_t *b, const uint8_
   if (!b->seq || !b->data_indices) return HPGQ_E_INVALID;
   HPGQ_HIP_TRY(hipSetDevice(q->device));
   using namespace hpgq::adapt;
-  constexpr int64_t kPart = (int64_t)1 << 28;   // reads per launch (32-bit offsets into idx; u32 cells)
-  const int rows = (int)q->rows;
-  for (int64_t lo = 0; lo < b->num_reads; lo += kPart) {
-    const int64_t n = std::min(kPart, b->num_reads - lo);
-    const int32_t *ix = b->data_indices + lo;
-    const uint8_t *mk = mask ? mask + lo : nullptr;
-    // persistent grid: as many workgroups per CU as stay resident (four of 512
-    // threads, fewer where the LDS -- 1 KB per probe, the 8 KB bitmap -- admits
-    // fewer of the 160 KB), no more than there are read groups
+  return hpgq::accum::for_parts(b, mask, [&](const int32_t *ix, const uint8_t *mk, int64_t n) {
+    // as many workgroups per CU as stay resident (four of 512 threads, fewer
+    // where the LDS -- 1 KB per probe, the 8 KB bitmap -- admits fewer of the
+    // 160 KB)
     const size_t lds = (size_t)q->pr.n * kP * 4 + kBitmapWords * 4 + 512;
     const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(4, (160 * 1024) / (int64_t)lds));
-    int64_t grid = std::min<int64_t>(per_cu * (int64_t)std::max(1, q->cus), (n + kGroup - 1) / kGroup);
-    if (q->max_wg > 0) grid = std::min<int64_t>(grid, q->max_wg);
+    const dim3 grid(q->grid(per_cu, (n + kGroup - 1) / kGroup));
     auto *k = mk ? (q->wide ? adapt_kernel<true, true> : adapt_kernel<true, false>)
                  : (q->wide ? adapt_kernel<false, true> : adapt_kernel<false, false>);
-    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(kWG), (size_t)q->pr.n * kP * 4, q->stream, b->seq, ix, n, mk, rows, q->pr, q->d_first,
-                       q->d_scal, q->d_flags);
-    HPGQ_HIP_TRY(hipGetLastError());
-  }
-  return HPGQ_OK;
+    hipLaunchKernelGGL(k, grid, dim3(kWG), (size_t)q->pr.n * kP * 4, q->stream, b->seq, ix, n, mk, (int)q->rows, q->pr,
+                       q->d_table, q->d_scal, q->d_flags);
+  });
 }
 
-int hpgq_adapt_sync(hpgq_adapt_t *q) {
-  if (!q) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  return a_settle(q);
-}
+int hpgq_adapt_sync(hpgq_adapt_t *q) { return q ? q->settle() : HPGQ_E_INVALID; }
 
-int hpgq_adapt_reset(hpgq_adapt_t *q) {
-  if (!q) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  HPGQ_HIP_TRY(hipMemsetAsync(q->d_first, 0, (size_t)q->rows * kRowBytes, q->stream));
-  HPGQ_HIP_TRY(hipMemsetAsync(q->d_scal, 0, 16, q->stream));
-  HPGQ_HIP_TRY(hipMemsetAsync(q->d_flags, 0, 8, q->stream));
-  return HPGQ_OK;
-}
+int hpgq_adapt_reset(hpgq_adapt_t *q) { return q ? q->reset() : HPGQ_E_INVALID; }
 
 int hpgq_adapt_read(hpgq_adapt_t *q, uint64_t *first, size_t n, hpgq_adapt_info_t *info) {
   if (!q || (!first && !info)) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  const int rc = a_settle(q);
+  int rc = q->settle();
   if (rc) return rc;
-  const size_t np = h_flags(q)[0];   // (<= rows: nothing clipped)
+  const size_t np = q->h_flags()[0];   // (<= rows: nothing clipped)
   const size_t na = (size_t)q->pr.n;
   if (info) {
     info->reads = q->h_scal[0];
@@ -492,16 +381,15 @@ int hpgq_adapt_read(hpgq_adapt_t *q, uint64_t *first, size_t n, hpgq_adapt_info_
   if (!np) return HPGQ_OK;
   // the device's rows are positions: transposed here into first[a * npos + p]
   std::vector<uint64_t> tmp(np * HPGQ_ADAPT_MAX_PROBES);
-  HPGQ_HIP_TRY(hipMemcpy(tmp.data(), q->d_first, np * kRowBytes, hipMemcpyDeviceToHost));
+  if ((rc = q->read_rows(tmp.data(), np)) != HPGQ_OK) return rc;
   for (size_t a = 0; a < na; ++a)
     for (size_t p = 0; p < np; ++p) first[a * np + p] = tmp[p * HPGQ_ADAPT_MAX_PROBES + a];
   return HPGQ_OK;
 }
 
 int hpgq_adapt_debug_set_max_workgroups(hpgq_adapt_t *q, int max_wg) {
-  if (!q || max_wg < 0) return HPGQ_E_INVALID;
-  q->max_wg = max_wg;
-  return HPGQ_OK;
+  return q ? q->set_max_workgroups(max_wg) : HPGQ_E_INVALID;
 }
 
 }  // extern "C"
+

@@ -35,7 +35,7 @@
 #include <rccl/rccl.h>
 #include <climits>
 #include <cstring>
-#include "hpgq_common.h"
+#include "hpgq_accum.h"
 
 #include <algorithm>
 #include <vector>
@@ -753,16 +753,14 @@ int hpgq_cgr_open(hpgq_cgr_t **cg, int device, int k, int base_quality) {
   if (!cg) return HPGQ_E_INVALID;
   *cg = nullptr;
   if (k < 1 || k > 12) return HPGQ_E_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return HPGQ_E_NO_DEVICE;
-  if (device < 0 || device >= ndev) return HPGQ_E_INVALID;
+  const int rc = hpgq::accum::use_device(device);
+  if (rc) return rc;
   hpgq_cgr *c = new hpgq_cgr();
   c->device = device;
   c->k = k;
   c->dim = 1 << k;
   c->base_quality = (uint32_t)base_quality;
   const size_t cells = (size_t)c->dim * c->dim;
-  HPGQ_HIP_TRY(hipSetDevice(device));
   HPGQ_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   HPGQ_HIP_TRY(hipMalloc(&c->d_ts, cells * 4));
   HPGQ_HIP_TRY(hipMalloc(&c->d_tq, cells * 4));

@@ -37,7 +37,8 @@
 // up again and copies the bytes of a read whose key has reached the threshold
 // and has no representative yet into the table's arena, once per key.
 // select_kernel compacts the slots at or above a count for hpgq_dup_top.
-#include "hpgq_common.h"
+#include "hpgq_accum.h"
+#include "hpgq_reads.h"
 
 #include <algorithm>
 #include <vector>
@@ -55,7 +56,7 @@ constexpr int kGroup = kWaves * kSegs;    // reads per workgroup step
 constexpr int kWaveRead = 2048;           // a longer read takes the whole wave
 constexpr int kLds = 1024;                // slots of insert_kernel's table in LDS (16 KB: 8 workgroups per CU)
 constexpr int kLdsProbes = 4;
-constexpr uint32_t kNone = 0xFFFFFFF0u;   // an offset past every descriptor: reads 0, no traffic
+using reads::kNone;
 constexpr uint64_t kG = 0x9E3779B97F4A7C15ULL;
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
@@ -77,7 +78,9 @@ __device__ inline u64 shfl_down64(u64 v, int d) {
 }
 
 // The five dwords from the dword-aligned byte `al` of the descriptor (`limit`
-// bytes): they cover any 16 bytes that start in the first of them.
+// bytes): they cover any 16 bytes that start in the first of them.  (Not
+// reads::lane_load8: a lane here takes 20 bytes, which may end further past
+// the read's end than the slack reaches, so it checks `limit` itself.)
 __device__ inline void lane_dwords(const __amdgpu_buffer_rsrc_t rs, uint32_t limit, uint32_t al, uint32_t &d0,
                                    uint32_t &d1, uint32_t &d2, uint32_t &d3, uint32_t &d4) {
   if (al + 20u <= limit) {
@@ -117,32 +120,21 @@ __device__ inline u64 lane_terms(const __amdgpu_buffer_rsrc_t rs, uint32_t limit
   return s;
 }
 
-// MASK: mask is not null (a compile-time choice, as in qdist_kernel)
+// MASK: mask is not null (a compile-time choice: hpgq_reads.h)
 template <bool MASK>
 __global__ void __launch_bounds__(kWG) fp_kernel(const char *seq, const int32_t *idx, int64_t n, const uint8_t *mask,
                                                  u64 *out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int seg = lane / kSeg, pos = lane - seg * kSeg;   // (lanes 60..63: segment 6, no read)
-  // the sequence bytes through a descriptor whose base is dword-aligned: the
-  // bytes of the first dword before `seq`, the bytes between reads and
-  // HPGQ_DEVICE_SLACK past the end are readable
-  const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(seq) & 3u);
-  const int32_t data_end = __builtin_amdgcn_readfirstlane(idx[n]);
-  const uint32_t limit = (uint32_t)data_end + shift + HPGQ_DEVICE_SLACK;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(seq - shift), (short)0, limit, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ri =
-      __builtin_amdgcn_make_buffer_rsrc((void *)idx, (short)0, (uint32_t)((n + 1) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rm =
-      __builtin_amdgcn_make_buffer_rsrc((void *)mask, (short)0, MASK ? (uint32_t)n : 0u, 0x00020000);
+  const reads::Batch rd = reads::open<MASK>(seq, idx, n, mask);
+  const __amdgpu_buffer_rsrc_t rs = rd.bytes;
+  const uint32_t shift = rd.shift, limit = rd.limit;
   const int64_t ngroups = (n + kGroup - 1) / kGroup;
   // (j + 1) G of the lane's first word in the first pass of its segment / of the whole wave
   const u64 seg_jg = (u64)(kLane / 8 * pos + 1) * kG, wave_jg = (u64)(kLane / 8 * lane + 1) * kG;
-  // lane l: offset of read rb + l (7 of them) and its mask byte; past the batch both read 0
+  // the offsets and mask bytes of workgroup step g
   auto offsets = [&](int64_t g, int32_t &ix, uint32_t &mk) {
-    const int64_t r = g * kGroup + wave * kSegs + lane;
-    ix = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ri, r <= n && lane <= kSegs ? (uint32_t)r * 4u : kNone, 0, 0);
-    const bool on = r < n && lane < kSegs;
-    mk = MASK ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rm, on ? (uint32_t)r : kNone, 0, 0) : (on ? 1u : 0u);
+    reads::step_reads<kSegs, MASK>(rd, g * kGroup + wave * kSegs, n, lane, ix, mk);
   };
   int32_t ix = 0, ix_next = 0;
   uint32_t mk = 0, mk_next = 0;
@@ -408,10 +400,10 @@ __global__ void __launch_bounds__(kWG) keep_kernel(const char *seq, const int32_
                                                    const u64 *tab, u64 *rep, u64 capmask, u64 min_count,
                                                    unsigned char *arena, u64 arena_bytes, u64 *state) {
   const int lane = threadIdx.x & 63;
-  const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(seq) & 3u);
-  const int32_t data_end = __builtin_amdgcn_readfirstlane(idx[n]);
-  const uint32_t limit = (uint32_t)data_end + shift + HPGQ_DEVICE_SLACK;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(seq - shift), (short)0, limit, 0x00020000);
+  // (the bytes alone: a lane reads its own read's two offsets with plain loads, and the keys are the mask)
+  const reads::Batch rd = reads::open<false>(seq, idx, n, nullptr);
+  const __amdgpu_buffer_rsrc_t rs = rd.bytes;
+  const uint32_t shift = rd.shift, limit = rd.limit;
   u64 kept = 0, kept_bytes = 0;   // (wave-uniform)
   bool lost = false;
   for (int64_t base = (int64_t)blockIdx.x * kWG; base < n; base += (int64_t)gridDim.x * kWG) {   // (uniform trip count)
@@ -496,8 +488,7 @@ __global__ void find_kernel(const u64 *tab, const u64 *rep, u64 capmask, u64 key
 struct hpgq_dup {
   int device = 0;
   int log2 = 0, log2_max = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  hpgq::accum::Stream stream;
   unsigned long long *d_tab = nullptr;     // [2^log2] {key, count}
   unsigned long long *d_state = nullptr;   // kStateWords words, see the enum
   unsigned long long *d_res = nullptr;     // levels_kernel's result
@@ -509,7 +500,7 @@ struct hpgq_dup {
   int64_t rehashes = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};   // hpgq_dup_debug_set_timing: before, between and after the kernels
   bool timing = false, timed = false;
-  std::vector<void *> retired;             // buffers replaced or lent to a kernel: freed once the stream is idle
+  hpgq::accum::Retired retired;            // buffers replaced or lent to a kernel
   // hpgq_dup_keep_sequences: keep_min == 0 is keeping off
   uint64_t keep_min = 0, arena_bytes = 0;
   unsigned long long *d_rep = nullptr;     // [2^log2] representative words, beside the slots
@@ -525,16 +516,14 @@ using namespace hpgq::dup;
 int d_settle(hpgq_dup *d) {
   HPGQ_HIP_TRY(hipMemcpyAsync(d->h_state, d->d_state, kStateWords * 8, hipMemcpyDeviceToHost, d->stream));
   HPGQ_HIP_TRY(hipStreamSynchronize(d->stream));
-  for (void *p : d->retired) (void)hipFree(p);
-  d->retired.clear();
+  d->retired.free_all();
   d->bound = d->h_state[kOccupied];
   return d->h_state[kError] & kErrFull ? HPGQ_E_STATE : HPGQ_OK;
 }
 
 unsigned grid_for(const hpgq_dup *d, uint64_t items, int per_wg) {
-  uint64_t g = std::min<uint64_t>(8 * (uint64_t)std::max(1, d->cus), (items + per_wg - 1) / per_wg);
-  if (d->max_wg > 0) g = std::min<uint64_t>(g, (uint64_t)d->max_wg);
-  return (unsigned)std::max<uint64_t>(g, 1);
+  const uint64_t g = std::min<uint64_t>(8 * (uint64_t)std::max(1, d->cus), (items + per_wg - 1) / per_wg);
+  return (unsigned)std::max<int64_t>(hpgq::accum::capped((int64_t)g, d->max_wg), 1);
 }
 
 // agg: the keys may repeat (fingerprints of reads), see insert_kernel
@@ -587,8 +576,8 @@ int d_room(hpgq_dup *d, uint64_t incoming) {
     d->d_tab = nt;
     d->d_rep = nr;
     d->log2 = k;
-    d->retired.push_back(old);   // the rehash below reads it
-    if (old_rep) d->retired.push_back(old_rep);
+    d->retired.add(old);   // the rehash below reads it
+    if (old_rep) d->retired.add(old_rep);
     ++d->rehashes;
     const int rc = d_insert(d, old, old + 1, old_cap, 2, false);   // (its claims count the occupied slots again)
     if (rc) return rc;
@@ -609,7 +598,7 @@ int d_fp_room(hpgq_dup *d, int64_t n) {
     (void)hipGetLastError();
     return HPGQ_E_NOMEM;
   }
-  if (d->d_fp) d->retired.push_back(d->d_fp);   // (a kernel in flight may still read it)
+  if (d->d_fp) d->retired.add(d->d_fp);   // (a kernel in flight may still read it)
   d->d_fp = p;
   d->fp_cap = n;
   return HPGQ_OK;
@@ -651,22 +640,15 @@ extern "C" {
 int hpgq_dup_open(hpgq_dup_t **dp, int device, int log2_slots, int log2_max_slots, void *stream) {
   if (!dp || log2_slots < 4 || log2_max_slots < log2_slots || log2_max_slots > 34) return HPGQ_E_INVALID;
   *dp = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return HPGQ_E_NO_DEVICE;
-  if (device < 0 || device >= ndev) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(device));
+  int rc = hpgq::accum::use_device(device);
+  if (rc) return rc;
   hpgq_dup *d = new hpgq_dup;
   d->device = device;
   d->log2 = log2_slots;
   d->log2_max = log2_max_slots;
-  if (stream) {
-    d->stream = (hipStream_t)stream;
-  } else {
-    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete d;
-      return HPGQ_E_HIP;
-    }
-    d->own_stream = true;
+  if ((rc = d->stream.open(stream)) != HPGQ_OK) {
+    delete d;
+    return rc;
   }
   const size_t hs = (size_t)(kStateWords + kLevelWords) * 8;
   if (hipMalloc(&d->d_tab, (size_t)16 << log2_slots) != hipSuccess || hipMalloc(&d->d_state, kStateWords * 8) != hipSuccess ||
@@ -691,7 +673,7 @@ void hpgq_dup_close(hpgq_dup_t *d) {
   if (!d) return;
   (void)hipSetDevice(d->device);
   if (d->stream) (void)hipStreamSynchronize(d->stream);
-  for (void *p : d->retired) (void)hipFree(p);
+  d->retired.free_all();
   (void)hipFree(d->d_tab);
   (void)hipFree(d->d_state);
   (void)hipFree(d->d_res);
@@ -701,7 +683,7 @@ void hpgq_dup_close(hpgq_dup_t *d) {
   if (d->h_state) (void)hipHostFree(d->h_state);
   for (hipEvent_t e : d->ev)
     if (e) (void)hipEventDestroy(e);
-  if (d->own_stream) (void)hipStreamDestroy(d->stream);
+  d->stream.close();
   delete d;
 }
 
@@ -825,7 +807,7 @@ int hpgq_dup_import(hpgq_dup_t *d, const uint64_t *keys, const uint64_t *counts,
     d->bound -= n;
     HPGQ_HIP_TRY(e);
   }
-  d->retired.push_back(dk);   // the kernel reads it
+  d->retired.add(dk);   // the kernel reads it
   return d_insert(d, dk, dk + n, (int64_t)n, 1, false);
 }
 

@@ -20,7 +20,7 @@
 //   gs_carry_kernel   the stream's last 16 codes become the next call's prefix
 //                     and the header flag is stored, so a text may be cut at
 //                     any byte and no call waits for the GPU.
-#include "hpgq_common.h"
+#include "hpgq_accum.h"
 
 #include <cstring>
 
@@ -379,8 +379,7 @@ struct hpgq_gs {
   int k = 0;
   int num_cus = 0;
   int max_wg = 0;              // hpgq_gs_debug_set_max_workgroups (0: no limit)
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  hpgq::accum::Stream stream;
   uint32_t *d_table = nullptr;
   hpgq::gs::State *d_state = nullptr;
   uint8_t *d_packed = nullptr; // [kPrefix | codes]
@@ -411,14 +410,11 @@ int hpgq_gs_open(hpgq_gs_t **gs, int device, int k, void *stream) {
   if (!gs) return HPGQ_E_INVALID;
   *gs = nullptr;
   if (k < 1 || k > 12) return HPGQ_E_INVALID;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return HPGQ_E_NO_DEVICE;
-  if (device < 0 || device >= ndev) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(device));
+  int rc = hpgq::accum::use_device(device);
+  if (rc) return rc;
   hpgq_gs *g = new hpgq_gs();
   g->device = device;
   g->k = k;
-  int rc = HPGQ_OK;
   auto fail = [&](int code) {
     hpgq_gs_close(g);
     return code;
@@ -426,12 +422,7 @@ int hpgq_gs_open(hpgq_gs_t **gs, int device, int k, void *stream) {
   if (hipDeviceGetAttribute(&g->num_cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess ||
       g->num_cus <= 0)
     return fail(HPGQ_E_HIP);
-  if (stream) {
-    g->stream = (hipStream_t)stream;
-  } else {
-    if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) return fail(HPGQ_E_HIP);
-    g->own_stream = true;
-  }
+  if ((rc = g->stream.open(stream)) != HPGQ_OK) return fail(rc);
   g->packed_cap = kPrefix + 4096;
   if (hipMalloc(&g->d_table, (size_t)4 << (2 * k)) != hipSuccess ||
       hipMalloc(&g->d_state, sizeof(State)) != hipSuccess ||
@@ -455,7 +446,7 @@ void hpgq_gs_close(hpgq_gs_t *g) {
     if (g->h_stage[i]) (void)hipHostFree(g->h_stage[i]);
     if (g->ev[i]) (void)hipEventDestroy(g->ev[i]);
   }
-  if (g->own_stream && g->stream) (void)hipStreamDestroy(g->stream);
+  g->stream.close();
   delete g;
 }
 

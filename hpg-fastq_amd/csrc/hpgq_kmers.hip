@@ -41,7 +41,8 @@
 //                       window gathers (one lane per read made
 //                       1024-read groups whose L2 re-reads doubled the HBM
 //                       traffic).
-#include "hpgq_common.h"
+#include "hpgq_accum.h"
+#include "hpgq_reads.h"
 
 #include <algorithm>
 #include <climits>
@@ -95,10 +96,8 @@ __device__ __forceinline__ bool counted(const uint8_t *mask, int64_t r) { return
 __global__ void __launch_bounds__(1024) kmer_maxlen_kernel(const int32_t *idx, int64_t n, const uint8_t *mask,
                                                            int *maxlen) {
   __shared__ int wm[16];
-  const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)idx, (short)0, (uint32_t)((n + 1) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)mask, (short)0, mask ? (uint32_t)n : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ri = reads::idx_rsrc(idx, n);
+  const __amdgpu_buffer_rsrc_t rm = reads::mask_rsrc(mask, n, mask != nullptr);
   int m = 0;
   for (int64_t r = 4 * ((int64_t)blockIdx.x * 1024 + threadIdx.x); r < n; r += 4 * (int64_t)gridDim.x * 1024) {
     if (r + 4 > n) {   // the last reads: one by one (a dword past n would read 0)
@@ -168,15 +167,16 @@ __global__ void __launch_bounds__(kWG) kmer_tile_kernel(const char *seq, const i
   // lanes of a group (lanes 0-31, 32-63: one LDS cycle each) sit on 32
   // distinct positions at every step
   const int q = (lane >> 1) & 15, hl = lane & 1;
+  // (not reads::open: this descriptor starts at `seq` itself -- the windows are
+  // cut to dwords counted from `seq`, no shift -- and meta_raw below has its
+  // own out-of-range offset, scaled by 4 after the choice)
   const int32_t data_end = __builtin_amdgcn_readfirstlane(idx[n]);
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
       (void *)seq, (short)0, data_end + HPGQ_DEVICE_SLACK, 0x00020000);
   // read offsets and mask through descriptors too: the loads past the batch
   // (the pipeline's prefetch past the last group) read 0 and move nothing
-  const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)idx, (short)0, (uint32_t)((n + 1) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)mask, (short)0, mask ? (uint32_t)n : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ri = reads::idx_rsrc(idx, n);
+  const __amdgpu_buffer_rsrc_t rm = reads::mask_rsrc(mask, n, mask != nullptr);
   const int64_t ngroups = (n + kGroup - 1) / kGroup;
   const int64_t gstride = 8 * (int64_t)classes;
   const int64_t g0 = xcd + 8 * (int64_t)cls;
@@ -361,10 +361,8 @@ __device__ __forceinline__ void long_reads_block(const LongArgs &L, int npos, in
   if (r0 < L.n) {
     // (through descriptors, as kmer_maxlen_kernel: any dword alignment; past
     // the batch the offsets read 0 and the mask bytes 0)
-    const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)L.idx, (short)0, (uint32_t)((L.n + 1) * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
-        (void *)L.mask, (short)0, L.mask ? (uint32_t)L.n : 0u, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ri = reads::idx_rsrc(L.idx, L.n);
+    const __amdgpu_buffer_rsrc_t rm = reads::mask_rsrc(L.mask, L.n, L.mask != nullptr);
     if (r0 + 4 <= L.n) {
       const v4u x = __builtin_amdgcn_raw_buffer_load_b128(ri, (uint32_t)r0 * 4u, 0, 0);
       a[0] = (int32_t)x[0]; a[1] = (int32_t)x[1]; a[2] = (int32_t)x[2]; a[3] = (int32_t)x[3];
@@ -467,8 +465,7 @@ constexpr size_t kKOvfChunk = 4096;
 struct hpgq_kmers {
   int device = 0;
   int lmax = 0, npos = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  hpgq::accum::Stream stream;
   unsigned long long *d_out = nullptr;
   int *d_maxlen = nullptr;   // per call: the longest counted read
   uint32_t *d_slab = nullptr;   // per tile workgroup: its table of the call
@@ -554,22 +551,15 @@ extern "C" {
 int hpgq_kmers_open(hpgq_kmers_t **km, int device, int lmax, void *stream) {
   if (!km || lmax < 1 || lmax > HPGQ_LMAX_LIMIT) return HPGQ_E_INVALID;
   *km = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return HPGQ_E_NO_DEVICE;
-  if (device < 0 || device >= ndev) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(device));
+  int rc = hpgq::accum::use_device(device);
+  if (rc) return rc;
   hpgq_kmers *k = new hpgq_kmers;
   k->device = device;
   k->lmax = lmax;
   k->npos = lmax > hpgq::kmers::kK - 1 ? lmax - (hpgq::kmers::kK - 1) : 0;
-  if (stream) {
-    k->stream = (hipStream_t)stream;
-  } else {
-    if (hipStreamCreateWithFlags(&k->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete k;
-      return HPGQ_E_HIP;
-    }
-    k->own_stream = true;
+  if ((rc = k->stream.open(stream)) != HPGQ_OK) {
+    delete k;
+    return rc;
   }
   const size_t bytes = (size_t)hpgq::kmers::kNum * (size_t)(k->npos > 0 ? k->npos : 1) * 8;
   if (hipMalloc(&k->d_out, bytes) != hipSuccess || hipMalloc(&k->d_maxlen, sizeof(int)) != hipSuccess ||
@@ -613,7 +603,7 @@ void hpgq_kmers_close(hpgq_kmers_t *k) {
   (void)hipFree(k->d_flags);
   if (k->h_flags) (void)hipHostFree(k->h_flags);
   for (uint32_t *q : k->ovf_chunks) (void)hipFree(q);
-  if (k->own_stream) (void)hipStreamDestroy(k->stream);
+  k->stream.close();
   delete k;
 }
 

@@ -24,7 +24,7 @@
 //   pair_check_kernel  one lane per pair compares the two header names in
 //                      16-byte windows; the lowest bad pair by wave reduction
 //                      and one atomicMin per wave
-#include "hpgq_common.h"
+#include "hpgq_accum.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -254,8 +254,7 @@ __global__ void __launch_bounds__(256) pair_check_kernel(NameSide A, NameSide B,
 
 struct hpgq_parser {
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  hpgq::accum::Stream stream;
   uint8_t *d_text = nullptr;
   size_t text_cap = 0;
   uint32_t *d_tiles = nullptr;   // counts, then offsets (+ total)
@@ -307,19 +306,18 @@ extern "C" {
 int hpgq_parser_open(hpgq_parser_t **ps, int device, void *stream) {
   if (!ps) return HPGQ_E_INVALID;
   *ps = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return HPGQ_E_NO_DEVICE;
-  if (device < 0 || device >= ndev) return HPGQ_E_INVALID;
+  int rc = hpgq::accum::use_device(device);
+  if (rc) return rc;
   hpgq_parser *p = new hpgq_parser();
   p->device = device;
-  HPGQ_HIP_TRY(hipSetDevice(device));
-  if (stream) {
-    p->stream = (hipStream_t)stream;
-  } else {
-    HPGQ_HIP_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-    p->own_stream = true;
+  if ((rc = p->stream.open(stream)) != HPGQ_OK) {
+    delete p;
+    return rc;
   }
-  HPGQ_HIP_TRY(hipMalloc(&p->d_bad, 8));
+  if (hipMalloc(&p->d_bad, 8) != hipSuccess) {
+    hpgq_parser_close(p);
+    return HPGQ_E_HIP;
+  }
   *ps = p;
   return HPGQ_OK;
 }
@@ -342,7 +340,7 @@ void hpgq_parser_close(hpgq_parser_t *p) {
   (void)hipFree(p->d_len2);
   (void)hipFree(p->d_seq2);
   (void)hipFree(p->d_qual2);
-  if (p->own_stream) (void)hipStreamDestroy(p->stream);
+  p->stream.close();
   delete p;
 }
 

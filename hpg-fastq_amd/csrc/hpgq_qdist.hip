@@ -32,7 +32,8 @@
 // The longest counted read goes to flags[0] (atomicMax, one per workgroup);
 // a counted read longer than the table's rows has only its positions below the
 // rows counted and adds 1 to flags[1] (hpgq_qdist_sync: HPGQ_E_READ_TOO_LONG).
-#include "hpgq_common.h"
+#include "hpgq_accum.h"
+#include "hpgq_reads.h"
 
 #include <algorithm>
 #include <climits>
@@ -47,30 +48,19 @@ constexpr int kWG = 512;
 constexpr int kWaves = kWG / 64;
 constexpr int kR = 16;      // reads per wave step
 constexpr int kGroup = kWaves * kR;   // reads per workgroup step
-constexpr uint32_t kNone = 0xFFFFFFF0u;   // an offset past every descriptor: reads 0, no traffic
-typedef unsigned v2u __attribute__((ext_vector_type(2)));
+using reads::v2u;
 static_assert((kP / 4) % 32 == 0, "a 32-lane group must span the 32 banks");
 static_assert(kP == 4 * 64, "lane l holds positions 4l..4l+3 of the tile");
 static_assert(kWin * kP * 4 == 65536, "the table is the whole static LDS");
 
-// MASK: mask is not null (a compile-time choice, as in kmer_tile_kernel)
+// MASK: mask is not null (a compile-time choice: hpgq_reads.h)
 template <bool MASK>
 __global__ void __launch_bounds__(kWG) qdist_kernel(const char *qual, const int32_t *idx, int64_t n,
                                                     const uint8_t *mask, int rows, int base,
                                                     unsigned long long *hist, uint32_t *flags) {
   __shared__ uint32_t t[kWin * kP];   // [value - base][permuted position]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // the quality bytes through a descriptor whose base is dword-aligned: the
-  // bytes of the first dword before `qual`, the bytes between reads and
-  // HPGQ_DEVICE_SLACK past the end are readable, and anything further reads 0
-  const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(qual) & 3u);
-  const int32_t data_end = __builtin_amdgcn_readfirstlane(idx[n]);
-  const __amdgpu_buffer_rsrc_t rq = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)(qual - shift), (short)0, (uint32_t)data_end + shift + HPGQ_DEVICE_SLACK, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ri = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)idx, (short)0, (uint32_t)((n + 1) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc(
-      (void *)mask, (short)0, MASK ? (uint32_t)n : 0u, 0x00020000);
+  const reads::Batch rd = reads::open<MASK>(qual, idx, n, mask);
   const int64_t ngroups = (n + kGroup - 1) / kGroup;
   int longest = 0;          // over this wave's counted reads (wave-uniform)
   uint32_t clipped = 0;     // its counted reads longer than the table
@@ -81,14 +71,9 @@ __global__ void __launch_bounds__(kWG) qdist_kernel(const char *qual, const int3
     for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
       const int64_t rb = g * kGroup + wave * kR;
       if (rb >= n) continue;
-      // lane l: offset of read rb + l (17 of them) and its mask byte; past the
-      // batch both read 0
-      const int64_t r = rb + lane;
-      const int32_t ix = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(
-          ri, r <= n && lane <= kR ? (uint32_t)r * 4u : kNone, 0, 0);
-      const bool on = r < n && lane < kR;
-      const uint32_t mk = MASK ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rm, on ? (uint32_t)r : kNone, 0, 0)
-                               : (on ? 1u : 0u);
+      int32_t ix;
+      uint32_t mk;
+      reads::step_reads<kR, MASK>(rd, rb, n, lane, ix, mk);
       v2u w[kR];
       uint32_t st[kR];   // the tile's first byte of read i, from the descriptor's base (wave-uniform)
       int rem[kR];       // its positions in this tile and after (<= 0: none; wave-uniform)
@@ -102,14 +87,10 @@ __global__ void __launch_bounds__(kWG) qdist_kernel(const char *qual, const int3
           clipped += len > rows ? 1u : 0u;
         }
         rem[i] = cnt ? min(len, rows) - p0 : 0;
-        st[i] = (uint32_t)a + shift + (uint32_t)p0;
-        // a lane that holds a position (4 l < rem) takes dwords l and l + 1 in
-        // one 8-byte load (dword-aligned; neighbours overlap by a dword, which
-        // the L1 serves: handing the neighbour's dword over by ds_bpermute was
-        // a fifth LDS instruction per read in a kernel the LDS atomics bound).
-        // Its last byte is at most 6 past the read's end: inside the slack.
-        const bool need = 4 * lane < rem[i];
-        w[i] = __builtin_amdgcn_raw_buffer_load_b64(rq, need ? (st[i] & ~3u) + 4u * (uint32_t)lane : kNone, 0, 0);
+        st[i] = (uint32_t)a + rd.shift + (uint32_t)p0;
+        // (handing the neighbour's dword over by ds_bpermute instead of loading
+        // it was a fifth LDS instruction per read in a kernel the LDS atomics bound)
+        w[i] = reads::lane_load8(rd.bytes, st[i], rem[i], lane);
       }
 #pragma unroll
       for (int i = 0; i < kR; ++i) {
@@ -165,30 +146,13 @@ __global__ void __launch_bounds__(kWG) qdist_kernel(const char *qual, const int3
 }  // namespace qdist
 }  // namespace hpgq
 
-struct hpgq_qdist {
-  int device = 0;
+// the table: hist[rows][256]
+struct hpgq_qdist : hpgq::accum::Positions {
   int base = 0;
-  int64_t rows = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  unsigned long long *d_hist = nullptr;   // [rows][256]
-  uint32_t *d_flags = nullptr;            // [longest counted read, counted reads longer than the rows]
-  uint32_t *h_flags = nullptr;            // their pinned copy
-  int cus = 0, max_wg = 0;
-  std::vector<void *> retired;            // tables replaced by a larger one: freed once the stream is idle
 };
 
 namespace {
 constexpr size_t kRowBytes = (size_t)HPGQ_QDIST_VALUES * 8;
-
-// wait for the stream, fetch the flags, free the replaced tables
-int q_settle(hpgq_qdist *q) {
-  HPGQ_HIP_TRY(hipMemcpyAsync(q->h_flags, q->d_flags, 8, hipMemcpyDeviceToHost, q->stream));
-  HPGQ_HIP_TRY(hipStreamSynchronize(q->stream));
-  for (void *p : q->retired) (void)hipFree(p);
-  q->retired.clear();
-  return q->h_flags[1] ? HPGQ_E_READ_TOO_LONG : HPGQ_OK;
-}
 }  // namespace
 
 extern "C" {
@@ -196,34 +160,13 @@ extern "C" {
 int hpgq_qdist_open(hpgq_qdist_t **qd, int device, int rows, int base, void *stream) {
   if (!qd || rows < 1 || base < 0 || base > HPGQ_QDIST_VALUES - hpgq::qdist::kWin) return HPGQ_E_INVALID;
   *qd = nullptr;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return HPGQ_E_NO_DEVICE;
-  if (device < 0 || device >= ndev) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(device));
+  int rc = hpgq::accum::use_device(device);
+  if (rc) return rc;
   hpgq_qdist *q = new hpgq_qdist;
-  q->device = device;
   q->base = base;
-  q->rows = rows;
-  if (stream) {
-    q->stream = (hipStream_t)stream;
-  } else {
-    if (hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking) != hipSuccess) {
-      delete q;
-      return HPGQ_E_HIP;
-    }
-    q->own_stream = true;
-  }
-  if (hipMalloc(&q->d_hist, (size_t)rows * kRowBytes) != hipSuccess || hipMalloc(&q->d_flags, 8) != hipSuccess ||
-      hipHostMalloc(reinterpret_cast<void **>(&q->h_flags), 8, hipHostMallocDefault) != hipSuccess) {
+  if ((rc = q->open(device, stream, rows, kRowBytes, 0)) != HPGQ_OK) {
     hpgq_qdist_close(q);
-    return HPGQ_E_NOMEM;
-  }
-  q->h_flags[0] = q->h_flags[1] = 0;
-  if (hipMemsetAsync(q->d_hist, 0, (size_t)rows * kRowBytes, q->stream) != hipSuccess ||
-      hipMemsetAsync(q->d_flags, 0, 8, q->stream) != hipSuccess ||
-      hipDeviceGetAttribute(&q->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
-    hpgq_qdist_close(q);
-    return HPGQ_E_HIP;
+    return rc;
   }
   *qd = q;
   return HPGQ_OK;
@@ -231,35 +174,12 @@ int hpgq_qdist_open(hpgq_qdist_t **qd, int device, int rows, int base, void *str
 
 void hpgq_qdist_close(hpgq_qdist_t *q) {
   if (!q) return;
-  (void)hipSetDevice(q->device);
-  if (q->stream) (void)hipStreamSynchronize(q->stream);
-  for (void *p : q->retired) (void)hipFree(p);
-  (void)hipFree(q->d_hist);
-  (void)hipFree(q->d_flags);
-  if (q->h_flags) (void)hipHostFree(q->h_flags);
-  if (q->own_stream) (void)hipStreamDestroy(q->stream);
+  q->close();
   delete q;
 }
 
 int hpgq_qdist_reserve_length(hpgq_qdist_t *q, int64_t max_len) {
-  if (!q || max_len < 0 || max_len > INT32_MAX) return HPGQ_E_INVALID;
-  if (max_len <= q->rows) return HPGQ_OK;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  // (half as much again at least: a file whose units grow slowly reallocates rarely)
-  const int64_t nr = std::min<int64_t>(std::max<int64_t>(max_len, q->rows + q->rows / 2), INT32_MAX);
-  unsigned long long *d = nullptr;
-  if (hipMalloc(&d, (size_t)nr * kRowBytes) != hipSuccess) return HPGQ_E_NOMEM;
-  const size_t old = (size_t)q->rows * kRowBytes;
-  if (hipMemcpyAsync(d, q->d_hist, old, hipMemcpyDeviceToDevice, q->stream) != hipSuccess ||
-      hipMemsetAsync(reinterpret_cast<char *>(d) + old, 0, (size_t)nr * kRowBytes - old, q->stream) != hipSuccess) {
-    (void)hipStreamSynchronize(q->stream);
-    (void)hipFree(d);
-    return HPGQ_E_HIP;
-  }
-  q->retired.push_back(q->d_hist);   // the copy above still reads it
-  q->d_hist = d;
-  q->rows = nr;
-  return HPGQ_OK;
+  return q ? q->reserve_length(max_len) : HPGQ_E_INVALID;
 }
 
 int hpgq_qdist_count_device(hpgq_qdist_t *q, const hpgq_batch_t *b, const uint8_t *mask) {
@@ -268,57 +188,32 @@ int hpgq_qdist_count_device(hpgq_qdist_t *q, const hpgq_batch_t *b, const uint8_
   if (!b->quality || !b->data_indices) return HPGQ_E_INVALID;
   HPGQ_HIP_TRY(hipSetDevice(q->device));
   using namespace hpgq::qdist;
-  constexpr int64_t kPart = (int64_t)1 << 28;   // reads per launch (32-bit offsets into idx; u32 cells)
-  const int rows = (int)q->rows;
-  for (int64_t lo = 0; lo < b->num_reads; lo += kPart) {
-    const int64_t n = std::min(kPart, b->num_reads - lo);
-    const int32_t *ix = b->data_indices + lo;
-    const uint8_t *mk = mask ? mask + lo : nullptr;
-    // persistent grid: two workgroups per CU (64 KB of LDS each), no more than there are read groups
-    int64_t grid = std::min<int64_t>(2 * (int64_t)std::max(1, q->cus), (n + kGroup - 1) / kGroup);
-    if (q->max_wg > 0) grid = std::min<int64_t>(grid, q->max_wg);
-    if (mk)
-      hipLaunchKernelGGL(qdist_kernel<true>, dim3((unsigned)grid), dim3(kWG), 0, q->stream, b->quality, ix, n, mk, rows,
-                         q->base, q->d_hist, q->d_flags);
-    else
-      hipLaunchKernelGGL(qdist_kernel<false>, dim3((unsigned)grid), dim3(kWG), 0, q->stream, b->quality, ix, n, mk,
-                         rows, q->base, q->d_hist, q->d_flags);
-    HPGQ_HIP_TRY(hipGetLastError());
-  }
-  return HPGQ_OK;
+  return hpgq::accum::for_parts(b, mask, [&](const int32_t *ix, const uint8_t *mk, int64_t n) {
+    // two workgroups per CU (64 KB of LDS each)
+    const dim3 grid(q->grid(2, (n + kGroup - 1) / kGroup));
+    hipLaunchKernelGGL(mk ? qdist_kernel<true> : qdist_kernel<false>, grid, dim3(kWG), 0, q->stream, b->quality, ix, n,
+                       mk, (int)q->rows, q->base, q->d_table, q->d_flags);
+  });
 }
 
-int hpgq_qdist_sync(hpgq_qdist_t *q) {
-  if (!q) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  return q_settle(q);
-}
+int hpgq_qdist_sync(hpgq_qdist_t *q) { return q ? q->settle() : HPGQ_E_INVALID; }
 
-int hpgq_qdist_reset(hpgq_qdist_t *q) {
-  if (!q) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  HPGQ_HIP_TRY(hipMemsetAsync(q->d_hist, 0, (size_t)q->rows * kRowBytes, q->stream));
-  HPGQ_HIP_TRY(hipMemsetAsync(q->d_flags, 0, 8, q->stream));
-  return HPGQ_OK;
-}
+int hpgq_qdist_reset(hpgq_qdist_t *q) { return q ? q->reset() : HPGQ_E_INVALID; }
 
 int hpgq_qdist_read(hpgq_qdist_t *q, uint64_t *hist, size_t n, int32_t *npos) {
   if (!q || !npos) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  const int rc = q_settle(q);
+  const int rc = q->settle();
   if (rc) return rc;
-  const size_t np = q->h_flags[0];   // (<= rows: nothing clipped)
+  const size_t np = q->h_flags()[0];   // (<= rows: nothing clipped)
   *npos = (int32_t)np;
   if (!hist) return HPGQ_OK;
   if (n < np * HPGQ_QDIST_VALUES) return HPGQ_E_INVALID;
-  if (np) HPGQ_HIP_TRY(hipMemcpy(hist, q->d_hist, np * kRowBytes, hipMemcpyDeviceToHost));
-  return HPGQ_OK;
+  return q->read_rows(hist, np);
 }
 
 int hpgq_qdist_debug_set_max_workgroups(hpgq_qdist_t *q, int max_wg) {
-  if (!q || max_wg < 0) return HPGQ_E_INVALID;
-  q->max_wg = max_wg;
-  return HPGQ_OK;
+  return q ? q->set_max_workgroups(max_wg) : HPGQ_E_INVALID;
 }
 
 }  // extern "C"
+

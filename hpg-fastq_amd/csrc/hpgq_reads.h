@@ -1,0 +1,80 @@
+// hpgq_reads.h — how a wave gets at the reads of a step (device side of the
+// per-read statistics: hpgq_qdist.hip, hpgq_adapt.hip, hpgq_dup.hip and the
+// descriptors of hpgq_kmers.hip).  Everything here is inlined
+// and wave-uniform but the lane's own offset, so the descriptors stay in SGPRs.
+//
+// What is readable.  A batch is n reads back to back in `bytes` (seq or
+// quality), read r at [idx[r], idx[r + 1]), with HPGQ_DEVICE_SLACK readable
+// bytes after idx[n].  The bytes go through a descriptor whose base is the
+// dword at or below `bytes` and whose range ends with the slack, so a lane may
+// load, dword-aligned, the bytes of the first dword before `bytes`, the bytes
+// between and inside other reads and the slack past the last one; anything
+// further -- kNone above all -- reads 0 and moves nothing.  The offsets and the
+// mask bytes go through descriptors of exactly (n + 1) * 4 and n bytes (no
+// mask: 0 bytes), so past the batch both read 0.
+#pragma once
+#include "hpgq_common.h"
+
+namespace hpgq {
+namespace reads {
+
+typedef unsigned v2u __attribute__((ext_vector_type(2)));
+
+constexpr uint32_t kNone = 0xFFFFFFF0u;   // an offset past every descriptor: reads 0, no traffic
+
+// the n + 1 offsets of a batch
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t idx_rsrc(const int32_t *idx, int64_t n) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)idx, (short)0, (uint32_t)((n + 1) * 4), 0x00020000);
+}
+
+// its n mask bytes; have: mask is not null
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mask_rsrc(const uint8_t *mask, int64_t n, bool have) {
+  return __builtin_amdgcn_make_buffer_rsrc((void *)mask, (short)0, have ? (uint32_t)n : 0u, 0x00020000);
+}
+
+// A batch as a wave reads it.  A byte at offset o of `bytes` is at o + shift of
+// the descriptor, which holds `limit` bytes.
+struct Batch {
+  __amdgpu_buffer_rsrc_t bytes, idx, mask;
+  uint32_t shift, limit;
+};
+
+// MASK: mask is not null (a compile-time choice, as in kmer_tile_kernel)
+template <bool MASK>
+__device__ __forceinline__ Batch open(const char *bytes, const int32_t *idx, int64_t n, const uint8_t *mask) {
+  Batch b;
+  b.shift = (uint32_t)(reinterpret_cast<uintptr_t>(bytes) & 3u);
+  const int32_t data_end = __builtin_amdgcn_readfirstlane(idx[n]);
+  b.bytes = __builtin_amdgcn_make_buffer_rsrc((void *)(bytes - b.shift), (short)0,
+                                              (uint32_t)data_end + b.shift + HPGQ_DEVICE_SLACK, 0x00020000);
+  b.idx = idx_rsrc(idx, n);
+  b.mask = mask_rsrc(mask, n, MASK);
+  b.limit = (uint32_t)data_end + b.shift + HPGQ_DEVICE_SLACK;
+  return b;
+}
+
+// A step's R reads from read `first` on, one coalesced load each: lane l takes
+// the offset of read first + l (l <= R: R + 1 of them) into ix and the read's
+// mask byte (l < R; no mask: 1) into mk.  Past the batch both read 0.
+template <int R, bool MASK>
+__device__ __forceinline__ void step_reads(const Batch &b, int64_t first, int64_t n, int lane, int32_t &ix,
+                                           uint32_t &mk) {
+  const int64_t r = first + lane;
+  ix = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(b.idx, r <= n && lane <= R ? (uint32_t)r * 4u : kNone, 0, 0);
+  const bool on = r < n && lane < R;
+  mk = MASK ? (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(b.mask, on ? (uint32_t)r : kNone, 0, 0) : (on ? 1u : 0u);
+}
+
+// The 8 bytes of lane `lane` in a step of 4 bytes per lane: dwords l and l + 1
+// from the dword at or below byte st of the descriptor; rem: the read's bytes
+// from st on (a lane with none of them loads nothing).  v_alignbyte(w[1], w[0],
+// st & 3) is then the read's bytes st + 4l .. st + 4l + 3.  Neighbours overlap
+// by a dword, which the L1 serves.  The last byte is at most 6 past the read's
+// end: inside the slack.
+__device__ __forceinline__ v2u lane_load8(const __amdgpu_buffer_rsrc_t bytes, uint32_t st, int rem, int lane) {
+  const bool need = 4 * lane < rem;
+  return __builtin_amdgcn_raw_buffer_load_b64(bytes, need ? (st & ~3u) + 4u * (uint32_t)lane : kNone, 0, 0);
+}
+
+}  // namespace reads
+}  // namespace hpgq

@@ -35,8 +35,65 @@ def device_batch(num_reads, seq_ptr, qual_ptr, idx_ptr):
     return Batch(int(num_reads), int(seq_ptr), int(qual_ptr), int(idx_ptr))
 
 
-class Engine:
+class _Handle:
+    """A libhpgq handle.  `_prefix` names the class's C functions: <prefix>_open,
+    <prefix>_close and, where the C library has them, the pass-through methods
+    below (a class whose prefix lacks one raises AttributeError from the
+    library lookup)."""
+
+    _prefix = None
+    _h = None   # (the class's default: close and __del__ are safe when __init__ raised before the handle existed)
+
+    def _open(self, *args):
+        name = self._prefix + "_open"
+        h = C.c_void_p()
+        check(getattr(lib, name)(C.byref(h), *args), name)
+        self._h = h
+
+    def _call(self, what, *args):
+        name = f"{self._prefix}_{what}"
+        check(getattr(lib, name)(self._h, *args), name)
+
+    def close(self):
+        if self._h:
+            getattr(lib, self._prefix + "_close")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def sync(self):
+        self._call("sync")
+
+    def reset(self):
+        self._call("reset")
+
+    def set_max_workgroups(self, max_wg):
+        """<prefix>_debug_set_max_workgroups: at most max_wg workgroups per
+        launch (0: no limit); tests only."""
+        self._call("debug_set_max_workgroups", int(max_wg))
+
+    def count_device(self, batch, mask_ptr=None):
+        self._call("count_device", C.byref(batch), mask_ptr)
+
+    def reserve_length(self, max_len):
+        """<prefix>_reserve_length: room for reads of up to max_len."""
+        self._call("reserve_length", int(max_len))
+
+
+class Engine(_Handle):
     """One hpgq_ctx: a HIP stream + device counters on `device`."""
+
+    _prefix = "hpgq"
 
     def __init__(self, params, device=0, route=None):
         if not isinstance(params, Params):
@@ -44,9 +101,7 @@ class Engine:
         self.params = params
         self.lmax = params.lmax
         self.nsets = 2 if params.paired else 1
-        h = C.c_void_p()
-        check(lib.hpgq_open(C.byref(h), device, C.byref(params)), "hpgq_open")
-        self._h = h
+        self._open(device, C.byref(params))
         route = route if route is not None else DEFAULT_ROUTE
         if route is not None and route != "auto":
             self.set_route(route)
@@ -56,11 +111,6 @@ class Engine:
         'hex' / 'wide' first, 'auto_fixed' (no adaptive first stage)."""
         check(lib.hpgq_debug_set_route(self._h, ROUTES[route]), "hpgq_debug_set_route")
 
-    def set_max_workgroups(self, n):
-        """hpgq_debug_set_max_workgroups: at most n workgroups per stage (0: no
-        limit); tests only."""
-        check(lib.hpgq_debug_set_max_workgroups(self._h, int(n)), "hpgq_debug_set_max_workgroups")
-
     def stage_waves(self, stage, chain=0):
         """hpgq_debug_stage_waves -> (waves the stage launches at most, reads
         per unit it iterates over); stage 1..3, or 4 for the long-read tail's
@@ -69,23 +119,6 @@ class Engine:
         check(lib.hpgq_debug_stage_waves(self._h, int(chain), int(stage), C.byref(w), C.byref(b)),
               "hpgq_debug_stage_waves")
         return w.value, b.value
-
-    def close(self):
-        if self._h:
-            lib.hpgq_close(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     @property
     def stream(self):
@@ -125,16 +158,6 @@ class Engine:
     def run_device(self, batch, batch2=None, mask_ptr=None, trim_ptr=None):
         check(lib.hpgq_run_device(self._h, C.byref(batch), C.byref(batch2) if batch2 else None,
                                   mask_ptr, trim_ptr), "hpgq_run_device")
-
-    def sync(self):
-        check(lib.hpgq_sync(self._h), "hpgq_sync")
-
-    def reset(self):
-        check(lib.hpgq_reset(self._h), "hpgq_reset")
-
-    def reserve_length(self, max_len):
-        """hpgq_reserve_length: the long-read tail for merged reads up to max_len."""
-        check(lib.hpgq_reserve_length(self._h, int(max_len)), "hpgq_reserve_length")
 
     def counters(self):
         n = lib.hpgq_counters_size(self._h)
@@ -194,27 +217,16 @@ def summary(counter_set, lmax):
     return {f: getattr(s, f) for f, _ in Summary._fields_}
 
 
-class ChaosGame:
+class ChaosGame(_Handle):
     """hpgq_cgr: chaos_game_fill_tables on the device (old/chaos_game.c:165)."""
+
+    _prefix = "hpgq_cgr"
 
     def __init__(self, k, base_quality=33, device=0, path=0):
         self.k = k
         self.dim = 1 << k
-        h = C.c_void_p()
-        check(lib.hpgq_cgr_open(C.byref(h), device, k, base_quality), "hpgq_cgr_open")
-        self._h = h
-        check(lib.hpgq_cgr_set_path(h, path), "hpgq_cgr_set_path")
-
-    def close(self):
-        if self._h:
-            lib.hpgq_cgr_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._open(device, k, base_quality)
+        self._call("set_path", path)
 
     @property
     def stream(self):
@@ -223,12 +235,6 @@ class ChaosGame:
     def fill_device(self, batch, status_ptr=None, mode=CGR_ALL_READS):
         check(lib.hpgq_cgr_fill_device(self._h, C.byref(batch), status_ptr, mode),
               "hpgq_cgr_fill_device")
-
-    def sync(self):
-        check(lib.hpgq_cgr_sync(self._h), "hpgq_cgr_sync")
-
-    def reset(self):
-        check(lib.hpgq_cgr_reset(self._h), "hpgq_cgr_reset")
 
     def comm_init(self, nranks, rank, uid):
         """RCCL communicator for the table sum (uid from comm_unique_id())."""
@@ -315,45 +321,21 @@ def cgr_write_images(report_dir, fq_path, k, table_seq, table_q, fq_words, table
           "hpgq_cgr_write_images")
 
 
-class Kmers:
+class Kmers(_Handle):
     """hpgq_kmers: `stats --kmers` 5-mer counts per start position
     (merge src/stats_fastq.c:384-410; build-defined per-read rule)."""
+
+    _prefix = "hpgq_kmers"
 
     def __init__(self, lmax, device=0, stream=None):
         self.lmax = lmax
         self.npos = max(lmax - 4, 0)
-        h = C.c_void_p()
-        check(lib.hpgq_kmers_open(C.byref(h), device, lmax, stream), "hpgq_kmers_open")
-        self._h = h
-
-    def close(self):
-        if self._h:
-            lib.hpgq_kmers_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def count_device(self, batch, mask_ptr=None):
-        check(lib.hpgq_kmers_count_device(self._h, C.byref(batch), mask_ptr),
-              "hpgq_kmers_count_device")
-
-    def sync(self):
-        check(lib.hpgq_kmers_sync(self._h), "hpgq_kmers_sync")
-
-    def reset(self):
-        check(lib.hpgq_kmers_reset(self._h), "hpgq_kmers_reset")
+        self._open(device, lmax, stream)
 
     def by_pos(self):
         out = np.zeros((1024, self.npos), dtype=np.uint64)
         check(lib.hpgq_kmers_read(self._h, _ptr(out), out.size), "hpgq_kmers_read")
         return out
-
-    def reserve_length(self, max_len):
-        check(lib.hpgq_kmers_reserve_length(self._h, int(max_len)), "hpgq_kmers_reserve_length")
 
     def by_pos_ext(self):
         """hpgq_kmers_read_ext: every start, [1024, npos_ext]."""
@@ -364,51 +346,17 @@ class Kmers:
         return out
 
 
-class QualityDist:
+class QualityDist(_Handle):
     """hpgq_qdist: `stats --quality-dist`, bases per (read position, raw quality
     byte) of the counted reads.  `rows` positions are reserved
     (reserve_length grows them); `base` is a speed hint: the 64 byte values from
-    it are counted on chip."""
+    it are counted on chip.  sync(): HpgqError -4 after a counted read longer
+    than the rows, until reset()."""
+
+    _prefix = "hpgq_qdist"
 
     def __init__(self, rows, base=33, device=0, stream=None):
-        self._h = None
-        h = C.c_void_p()
-        check(lib.hpgq_qdist_open(C.byref(h), device, rows, base, stream), "hpgq_qdist_open")
-        self._h = h
-
-    def close(self):
-        if self._h:
-            lib.hpgq_qdist_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def count_device(self, batch, mask_ptr=None):
-        check(lib.hpgq_qdist_count_device(self._h, C.byref(batch), mask_ptr), "hpgq_qdist_count_device")
-
-    def reserve_length(self, max_len):
-        check(lib.hpgq_qdist_reserve_length(self._h, int(max_len)), "hpgq_qdist_reserve_length")
-
-    def sync(self):
-        """HpgqError -4 after a counted read longer than the rows, until reset()."""
-        check(lib.hpgq_qdist_sync(self._h), "hpgq_qdist_sync")
-
-    def reset(self):
-        check(lib.hpgq_qdist_reset(self._h), "hpgq_qdist_reset")
-
-    def set_max_workgroups(self, max_wg):
-        check(lib.hpgq_qdist_debug_set_max_workgroups(self._h, max_wg),
-              "hpgq_qdist_debug_set_max_workgroups")
+        self._open(device, rows, base, stream)
 
     def hist(self):
         """u64 [npos, 256], npos = the longest counted read (synchronises)."""
@@ -451,54 +399,21 @@ def qdist_quantiles(hist, phred):
     return out
 
 
-class AdapterContent:
+class AdapterContent(_Handle):
     """hpgq_adapt: `stats --adapters`, per probe the counted reads whose first
     occurrence of it starts at each read position.  `probes`:
     byte strings of 8 .. 32 A C G T, at most 32 of them (None: the default
-    set).  `rows` positions are reserved (reserve_length grows them)."""
+    set).  `rows` positions are reserved (reserve_length grows them).  sync():
+    HpgqError -4 after a counted read longer than the rows, until reset()."""
+
+    _prefix = "hpgq_adapt"
 
     def __init__(self, probes=None, rows=1024, device=0, stream=None):
-        self._h = None
         if probes is None:
             probes = [p for _, p in adapt_defaults()]
         self.probes = [p.encode() if isinstance(p, str) else bytes(p) for p in probes]
         arr = (C.c_char_p * max(len(self.probes), 1))(*self.probes)
-        h = C.c_void_p()
-        check(lib.hpgq_adapt_open(C.byref(h), device, arr, len(self.probes), rows, stream), "hpgq_adapt_open")
-        self._h = h
-
-    def close(self):
-        if self._h:
-            lib.hpgq_adapt_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def count_device(self, batch, mask_ptr=None):
-        check(lib.hpgq_adapt_count_device(self._h, C.byref(batch), mask_ptr), "hpgq_adapt_count_device")
-
-    def reserve_length(self, max_len):
-        check(lib.hpgq_adapt_reserve_length(self._h, int(max_len)), "hpgq_adapt_reserve_length")
-
-    def sync(self):
-        """HpgqError -4 after a counted read longer than the rows, until reset()."""
-        check(lib.hpgq_adapt_sync(self._h), "hpgq_adapt_sync")
-
-    def reset(self):
-        check(lib.hpgq_adapt_reset(self._h), "hpgq_adapt_reset")
-
-    def set_max_workgroups(self, max_wg):
-        check(lib.hpgq_adapt_debug_set_max_workgroups(self._h, max_wg), "hpgq_adapt_debug_set_max_workgroups")
+        self._open(device, arr, len(self.probes), rows, stream)
 
     def table(self):
         """(first u64 [nprobes, npos], dict(reads, with_any, nprobes, npos)); npos =
@@ -548,46 +463,16 @@ def _levels_dict(lv):
                 distinct_at=[int(x) for x in lv.distinct_at], reads_at=[int(x) for x in lv.reads_at])
 
 
-class Duplication:
+class Duplication(_Handle):
     """hpgq_dup: `stats --duplication`, the multiset {fingerprint -> count} of
     the counted reads' sequences in a device hash table.  The
-    table starts at 2^log2_slots slots and doubles up to 2^log2_max_slots."""
+    table starts at 2^log2_slots slots and doubles up to 2^log2_max_slots
+    (count_device: HpgqError -3 when it would have to grow past that)."""
+
+    _prefix = "hpgq_dup"
 
     def __init__(self, log2_slots=20, log2_max_slots=32, device=0, stream=None):
-        self._h = None
-        h = C.c_void_p()
-        check(lib.hpgq_dup_open(C.byref(h), device, log2_slots, log2_max_slots, stream), "hpgq_dup_open")
-        self._h = h
-
-    def close(self):
-        if self._h:
-            lib.hpgq_dup_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def count_device(self, batch, mask_ptr=None):
-        """HpgqError -3 when the table would have to grow past 2^log2_max_slots."""
-        check(lib.hpgq_dup_count_device(self._h, C.byref(batch), mask_ptr), "hpgq_dup_count_device")
-
-    def sync(self):
-        check(lib.hpgq_dup_sync(self._h), "hpgq_dup_sync")
-
-    def reset(self):
-        check(lib.hpgq_dup_reset(self._h), "hpgq_dup_reset")
-
-    def set_max_workgroups(self, max_wg):
-        check(lib.hpgq_dup_debug_set_max_workgroups(self._h, max_wg), "hpgq_dup_debug_set_max_workgroups")
+        self._open(device, log2_slots, log2_max_slots, stream)
 
     def levels(self):
         """dict: reads, distinct, max_count, distinct_at[16], reads_at[16] (synchronises)."""
@@ -714,34 +599,16 @@ def dup_top_of(keys, counts, n, min_count=1):
     return ok[:m], oc[:m], total.value
 
 
-class Signature:
+class Signature(_Handle):
     """hpgq_gs: the genomic signature of FASTA text, the table
     a --gs-filename file holds.  The text may be cut anywhere between add()s."""
+
+    _prefix = "hpgq_gs"
 
     def __init__(self, k, device=0, stream=None):
         self.k = k
         self.dim = 1 << k
-        self._h = None
-        h = C.c_void_p()
-        check(lib.hpgq_gs_open(C.byref(h), device, k, stream), "hpgq_gs_open")
-        self._h = h
-
-    def close(self):
-        if self._h:
-            lib.hpgq_gs_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        self._open(device, k, stream)
 
     def add(self, text):
         """bytes-like host text (staged; reusable on return) or a device uint8
@@ -754,16 +621,6 @@ class Signature:
         else:
             b = bytes(text)
             check(lib.hpgq_gs_add_host(self._h, b, len(b)), "hpgq_gs_add_host")
-
-    def sync(self):
-        check(lib.hpgq_gs_sync(self._h), "hpgq_gs_sync")
-
-    def reset(self):
-        check(lib.hpgq_gs_reset(self._h), "hpgq_gs_reset")
-
-    def set_max_workgroups(self, max_wg):
-        check(lib.hpgq_gs_debug_set_max_workgroups(self._h, max_wg),
-              "hpgq_gs_debug_set_max_workgroups")
 
     def table(self):
         """u32 [dim, dim], [co_x][co_y] (synchronises)."""
@@ -791,32 +648,15 @@ def record_prefix(buf, max_records):
     return int(n), int(r.value)
 
 
-class Parser:
+class Parser(_Handle):
     """hpgq_parser: FASTQ text -> device batch (parsing half of fastq_fread_se,
     src/stats_fastq.c:183, on the GPU)."""
 
+    _prefix = "hpgq_parser"
+
     def __init__(self, device=0, stream=None):
-        h = C.c_void_p()
-        check(lib.hpgq_parser_open(C.byref(h), device, stream), "hpgq_parser_open")
-        self._h = h
+        self._open(device, stream)
         self.num_reads = 0
-
-    def close(self):
-        if self._h:
-            lib.hpgq_parser_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
 
     def parse(self, text):
         """Host bytes (whole records) -> device Batch (valid until the next parse)."""
@@ -843,10 +683,6 @@ class Parser:
         if rc != E_PAIRING:
             check(rc, "hpgq_parse_pair_check")
         return int(bad.value)
-
-    def set_max_workgroups(self, max_wg):
-        check(lib.hpgq_parser_debug_set_max_workgroups(self._h, max_wg),
-              "hpgq_parser_debug_set_max_workgroups")
 
     @property
     def max_length(self):
