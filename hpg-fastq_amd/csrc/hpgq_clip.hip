@@ -1,0 +1,612 @@
+// hpgq_clip.hip — `edit --clip-adapters`: cut every read at the lowest position
+// at which a probe matches, whole or running off the read's end (DESIGN.md
+// §2.12, §4.15).  Build-defined: the reference has nothing like it.
+//
+// Three launches on the handle's stream, none of which waits on another
+// workgroup:
+//
+//   clip_find_kernel   per read the clip position c, the winning probe, and the
+//                      four scalars.  It reads the sequence bytes and the
+//                      offsets (L + 4 bytes per read).
+//   hipcub inclusive sum of the c into idx_out[1 .. n], idx_out[0] = 0
+//   clip_copy_kernel   sequence and quality [idx[i], idx[i] + c_i) to
+//                      [idx_out[i], idx_out[i + 1]).
+//
+// Find.  The step is hpgq_adapt.hip's (a wave takes kR = 16 reads, one after the
+// other; lane l takes the read's bytes p0 + 4l .. p0 + 4l + 3, packed into 2-bit
+// codes and validity bits, windows built across lanes with ds_bpermute; the
+// workgroup's bitmap of the set's 8-base prefixes ends most steps after one
+// ballot), with these differences:
+//   * a read ends at its first hit.  A step with candidates walks them, lowest
+//     start first: the start's window goes to every lane (v_readlane), lane a
+//     compares probe a (the probe parameters already sit in lanes 0 .. 31), and
+//     one ballot gives the lowest probe that matches there.  No found-mask lives
+//     across steps, there is no table, and a probe longer than 13 bases costs
+//     its three extra ds_bpermute only in a step that has a candidate.
+//   * a probe also matches where the read ends inside it.  With m = min(K, n - j)
+//     bases compared, the start passes the prefilter whenever m >= 8 (the bytes
+//     past the read's end are zeroed, so invalid: the valid run from j ends at
+//     the read's end), and the compare is under the mask of m bases.
+//   * matches of fewer than 8 bases (min_overlap < 8 only) start in the read's
+//     last 7 positions, behind every start the steps can hit.  A read without a
+//     hit gets one more load of its last 7 bytes; lane a compares probe a, one
+//     ballot per start.
+//
+// Copy.  Read-major, kR reads per wave step.  Source and destination have any
+// byte alignment, and reads of 0 .. 3 kept bases make several reads share one
+// output dword, so no partial dword is ever read, modified and written: the
+// dwords that lie whole inside a read's output range are assembled with
+// v_alignbyte from two source dwords and stored as dwords; the up to three bytes
+// before and after them are stored as bytes.  Every store is a vector store
+// inside [idx_out[i], idx_out[i + 1]) of its read.
+#include "hpgq_accum.h"
+#include "hpgq_reads.h"
+
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstring>
+
+namespace hpgq {
+namespace clip {
+
+constexpr int kMaxProbes = HPGQ_ADAPT_MAX_PROBES;
+constexpr int kWG = 512;
+constexpr int kWaves = kWG / 64;
+constexpr int kR = 16;      // reads per wave step
+constexpr int kPre = 4;     // of them with their first load in flight
+constexpr int kGroup = kWaves * kR;   // reads per workgroup step
+constexpr int kNarrowMax = 13;        // longest probe of the 32-bit window: 16 bases less the 3 a start may skip
+constexpr int kPrefix = 8;            // bases of the prefilter: HPGQ_ADAPT_MIN_LEN
+constexpr int kBitmapWords = 65536 / 32;   // one bit per 8-base prefix (16 code bits)
+constexpr int kScalars = 3 + kMaxProbes;   // reads, clipped, bases_removed, by_probe[32]
+using reads::v2u;
+static_assert(kR % kPre == 0, "the reads of a wave step go in blocks of kPre");
+static_assert(kPrefix == HPGQ_ADAPT_MIN_LEN, "every probe has the prefilter's bases");
+
+// the probe set as the kernel takes it (by value: scalar loads)
+struct Probes {
+  uint64_t code[kMaxProbes];   // base j at bits 2j .. 2j + 1
+  uint32_t len[kMaxProbes];
+  int32_t n, kmin, min_ov;
+};
+
+// the 2-bit code of an A C G T byte
+__host__ __device__ inline uint32_t code_of(uint32_t b) { return (b >> 1) & 3u; }
+
+__device__ __forceinline__ uint32_t pull(uint32_t v, int lane, int d) {
+  return (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + d) & 63) * 4, (int)v);
+}
+
+// The lane's four bytes v (those past the read's end zeroed) as four 2-bit
+// codes c (base j at bits 2j .. 2j + 1) and four validity bits ok (base j at bit
+// j): the byte is exactly the one base with its code.
+__device__ __forceinline__ void pack4(uint32_t v, uint32_t &c, uint32_t &ok) {
+  const uint32_t x = v >> 1 & 0x03030303u;
+  const uint32_t isT = x >> 1 & ~x & 0x01010101u;
+  const uint32_t d = v ^ (0x41414141u + 2u * x + 15u * isT);
+  const uint32_t z = ~(((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
+  c = (x | x >> 6 | x >> 12 | x >> 18) & 0xFFu;
+  ok = (z >> 7 | z >> 14 | z >> 21 | z >> 28) & 0xFu;
+}
+
+// the lane's bytes st + 4 lane .. + 3 of a read with rem bytes from st on
+__device__ __forceinline__ uint32_t lane_bytes(v2u w, uint32_t st, int rem, int lane) {
+  const int nb = rem - 4 * lane;
+  const uint32_t raw = __builtin_amdgcn_alignbyte(w[1], w[0], st & 3u);
+  return nb >= 4 ? raw : nb <= 0 ? 0u : raw & ((1u << (8 * nb)) - 1u);
+}
+
+// One read of len bytes at st0 (from the descriptor's base); w0: its first
+// step's load.  Everything but the lane's bytes is wave-uniform.  -> c, and the
+// winning probe in `who` (0xFF: none).
+template <bool WIDE>
+__device__ __forceinline__ int find_read(const __amdgpu_buffer_rsrc_t rq, const Probes &pr, int lane, uint32_t st0, int len,
+                                         v2u w0, uint32_t pc_lo, uint32_t pc_hi, uint32_t pk, const uint32_t *bm,
+                                         uint32_t &who) {
+  constexpr int H = WIDE ? 8 : 3;          // lanes after its own a lane's windows reach into
+  constexpr int S = 4 * (64 - H);          // starts per step
+  // the fewest bases a match of the steps compares: a whole probe, or an overlap that passes the prefilter
+  const int least = min(pr.kmin, max(pr.min_ov, kPrefix));
+  for (int p0 = 0; p0 + least <= len; p0 += S) {
+    const int rem = len - p0;
+    const uint32_t st = st0 + (uint32_t)p0;
+    const v2u w = p0 == 0 ? w0 : reads::lane_load8(rq, st, rem, lane);
+    uint32_t c, ok;
+    pack4(lane_bytes(w, st, rem, lane), c, ok);
+    // 16 bases from lanes l .. l + 3: codes 32 bits, validity 16
+    const uint32_t x1 = c | ok << 8;
+    const uint32_t y1 = pull(x1, lane, 1);
+    const uint32_t c2 = c | (y1 & 0xFFu) << 8, ok2 = ok | (y1 >> 8 & 0xFu) << 4;
+    const uint32_t y2 = pull(c2 | ok2 << 16, lane, 2);
+    const uint32_t c4 = c2 | y2 << 16, ok4 = ok2 | (y2 >> 16 & 0xFFu) << 8;
+    // Prefilter: a match of the steps compares at least 8 bases, so it can start
+    // only where the next 8 bases are valid (r8) and their 16 code bits are the
+    // first 8 bases of some probe (one bit of bm).  The lane's own 16 bases
+    // decide that, whatever the probes' lengths.
+    const bool starts = lane < 64 - H;   // the last H lanes only supply bases
+    const uint32_t r2 = ok4 & ok4 >> 1, r4 = r2 & r2 >> 2, r8 = r4 & r4 >> 4;
+    uint32_t cand = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint32_t ix8 = c4 >> (2 * k) & 0xFFFFu;
+      cand |= (bm[ix8 >> 5] >> (ix8 & 31u) & r8 >> k & 1u) << k;
+    }
+    unsigned long long lanes = __ballot(starts && cand != 0);
+    if (!lanes) continue;   // nothing starts in this step
+    // WIDE: the bases of lanes l + 4 .. l + 8 behind the lane's 16 (only a step with a candidate needs them)
+    uint32_t c8_hi = 0, ok8_hi = 0, y9 = 0;
+    if (WIDE) {
+      c8_hi = pull(c4, lane, 4);
+      ok8_hi = pull(ok4, lane, 4);
+      y9 = pull(x1, lane, 8);
+    }
+    // The candidates, lowest first: the window of one start goes to every lane,
+    // lane a compares probe a, and one ballot gives the lowest probe that matches
+    // there.  The first start with a match is c.
+    do {
+      const int l0 = __builtin_ctzll(lanes);
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)c4, l0);
+      const uint32_t vlo = (uint32_t)__builtin_amdgcn_readlane((int)ok4, l0);
+      uint64_t base = lo;          // the bases from the lane's first on, 2 bits each (WIDE: 32 and 4 more in over)
+      uint32_t valid = vlo, over = 0, vover = 0;
+      if (WIDE) {
+        base |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)c8_hi, l0) << 32;
+        valid |= (uint32_t)__builtin_amdgcn_readlane((int)ok8_hi, l0) << 16;
+        const uint32_t y = (uint32_t)__builtin_amdgcn_readlane((int)y9, l0);
+        over = y & 0xFFu;
+        vover = y >> 8 & 0xFu;
+      }
+      for (uint32_t ks = (uint32_t)__builtin_amdgcn_readlane((int)cand, l0); ks; ks &= ks - 1u) {
+        const int k0 = __builtin_ctz(ks);
+        const uint64_t win = WIDE && k0 ? base >> (2 * k0) | (uint64_t)over << (64 - 2 * k0) : base >> (2 * k0);
+        const uint32_t val = WIDE && k0 ? valid >> k0 | vover << (32 - k0) : valid >> k0;
+        // the valid bases from the start on, as far as the window goes, and the
+        // read's bases from it on (bytes past the read's end are invalid: run <= left)
+        const uint32_t run = (uint32_t)__builtin_ctzll(~(uint64_t)val);
+        const uint32_t left = (uint32_t)min(rem - 4 * l0 - k0, 32);
+        // lane a: probe a's whole length, or what the read has left of it (8 or more: the start is a candidate)
+        const uint32_t cmp = min(pk, left);
+        bool eq;
+        if (WIDE) {
+          const uint64_t mask = cmp >= 32u ? ~0ull : (1ull << (2 * cmp)) - 1ull;
+          eq = ((win ^ ((uint64_t)pc_hi << 32 | pc_lo)) & mask) == 0;
+        } else {
+          eq = (((uint32_t)win ^ pc_lo) & ((1u << (2 * cmp)) - 1u)) == 0;
+        }
+        const unsigned long long hit =
+            __ballot(lane < pr.n && eq && run >= cmp && (cmp == pk || cmp >= (uint32_t)pr.min_ov));
+        if (hit) {
+          who = (uint32_t)__builtin_ctzll(hit);
+          return p0 + 4 * l0 + k0;
+        }
+      }
+      lanes &= lanes - 1ull;
+    } while (lanes);
+  }
+  // Overlaps of fewer than 8 bases: the read's last tn <= 7 bytes, all of which
+  // lie behind every start the steps above can hit.  Lane a holds probe a.
+  if (pr.min_ov < kPrefix && len >= pr.min_ov) {
+    const int ts = max(len - (kPrefix - 1), 0), tn = len - ts;
+    const uint32_t st = st0 + (uint32_t)ts;
+    uint32_t c, ok;
+    pack4(lane_bytes(reads::lane_load8(rq, st, tn, lane), st, tn, lane), c, ok);
+    const uint32_t tc = (uint32_t)__builtin_amdgcn_readlane((int)c, 0) | (uint32_t)__builtin_amdgcn_readlane((int)c, 1) << 8;
+    const uint32_t tok = (uint32_t)__builtin_amdgcn_readlane((int)ok, 0) | (uint32_t)__builtin_amdgcn_readlane((int)ok, 1) << 4;
+    for (int d = 0; tn - d >= pr.min_ov; ++d) {
+      const int m = tn - d;   // 1 .. 7 bases, fewer than any probe has
+      const uint32_t vm = (1u << m) - 1u, cm = (1u << (2 * m)) - 1u;
+      const bool eq = lane < pr.n && (tok >> d & vm) == vm && ((tc >> (2 * d) ^ pc_lo) & cm) == 0;
+      const unsigned long long hit = __ballot(eq);
+      if (hit) {
+        who = (uint32_t)__builtin_ctzll(hit);
+        return ts + d;
+      }
+    }
+  }
+  who = 0xFFu;
+  return len;
+}
+
+// WIDE: a probe longer than kNarrowMax (a compile-time choice)
+template <bool WIDE>
+__global__ void __launch_bounds__(kWG) clip_find_kernel(const char *seq, const int32_t *idx, int64_t n, const Probes pr,
+                                                        uint32_t *pos_out, uint8_t *probe_out, unsigned long long *scal) {
+  __shared__ uint32_t bm[kBitmapWords];     // bit i: some probe's first 8 bases have the code bits i
+  __shared__ uint32_t won[kMaxProbes];      // reads won per probe
+  __shared__ unsigned long long red[3 * kWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < kBitmapWords; i += kWG) bm[i] = 0;
+  if (threadIdx.x < kMaxProbes) won[threadIdx.x] = 0;
+  __syncthreads();
+  if ((int)threadIdx.x < pr.n) {
+    const uint32_t ix8 = (uint32_t)pr.code[threadIdx.x] & 0xFFFFu;
+    atomicOr(&bm[ix8 >> 5], 1u << (ix8 & 31u));
+  }
+  __syncthreads();
+  const reads::Batch rd = reads::open<false>(seq, idx, n, nullptr);
+  const int64_t ngroups = (n + kGroup - 1) / kGroup;
+  // lane a holds probe a: its code's halves and its length
+  const int pa = lane < pr.n ? lane : 0;
+  const uint32_t pc_lo = (uint32_t)pr.code[pa], pc_hi = (uint32_t)(pr.code[pa] >> 32), pk = pr.len[pa];
+  const int shortest = min(pr.kmin, pr.min_ov);   // a shorter read has no match
+  // over this wave's reads (wave-uniform; a launch has at most 2^28 reads and 2^31 bytes)
+  uint32_t nreads = 0, nclipped = 0, removed = 0;
+  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const int64_t rb = g * kGroup + wave * kR;
+    if (rb >= n) continue;
+    int32_t ix;
+    uint32_t mk;
+    reads::step_reads<kR, false>(rd, rb, n, lane, ix, mk);
+    auto first_load = [&](int i) {
+      const int32_t a = __builtin_amdgcn_readlane(ix, i);
+      const int32_t len = __builtin_amdgcn_readlane(ix, i + 1) - a;
+      const bool scan = (uint32_t)__builtin_amdgcn_readlane((int)mk, i) == 1u && len >= shortest;
+      return reads::lane_load8(rd.bytes, (uint32_t)a + rd.shift, scan ? len : 0, lane);
+    };
+    v2u wq[kPre];
+#pragma unroll
+    for (int j = 0; j < kPre; ++j) wq[j] = first_load(j);
+    nreads += (uint32_t)(n - rb < kR ? n - rb : kR);
+    // lane i: read i's result.  A read without a hit keeps its length and no
+    // winner, so only a hit costs the wave anything here.
+    int my_c = (int)pull((uint32_t)ix, lane, 1) - ix, my_who = 0xFF;
+    for (int i0 = 0; i0 < kR; i0 += kPre) {
+#pragma unroll
+      for (int j = 0; j < kPre; ++j) {
+        const int i = i0 + j;
+        const int32_t a = __builtin_amdgcn_readlane(ix, i);
+        const int32_t len = __builtin_amdgcn_readlane(ix, i + 1) - a;
+        const bool on = (uint32_t)__builtin_amdgcn_readlane((int)mk, i) == 1u;
+        const v2u w = wq[j];
+        if (i0 + kPre < kR) wq[j] = first_load(i + kPre);
+        if (!on) continue;   // past the batch (wave-uniform)
+        uint32_t who = 0xFFu;
+        int c = len;
+        if (len >= shortest) c = find_read<WIDE>(rd.bytes, pr, lane, (uint32_t)a + rd.shift, len, w, pc_lo, pc_hi, pk, bm, who);
+        if (c < len) {
+          ++nclipped;
+          removed += (uint32_t)(len - c);
+          if (lane == 0) atomicAdd(&won[who], 1u);
+          if (lane == i) {
+            my_c = c;
+            my_who = (int)who;
+          }
+        }
+      }
+    }
+    if (lane < kR && rb + lane < n) {
+      pos_out[rb + lane] = (uint32_t)my_c;
+      if (probe_out) probe_out[rb + lane] = (uint8_t)my_who;
+    }
+  }
+  if (lane == 0) {
+    red[wave] = nreads;
+    red[kWaves + wave] = nclipped;
+    red[2 * kWaves + wave] = removed;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    unsigned long long s = 0;
+    for (int w2 = 0; w2 < kWaves; ++w2) s += red[threadIdx.x * kWaves + w2];
+    if (s) atomicAdd(&scal[threadIdx.x], s);
+  } else if (threadIdx.x >= 64 && (int)threadIdx.x < 64 + pr.n) {
+    const uint32_t s = won[threadIdx.x - 64];
+    if (s) atomicAdd(&scal[3 + threadIdx.x - 64], (unsigned long long)s);
+  }
+}
+
+// The dwords that lie whole inside the output range [dst, dst + len) of one
+// read, from s0 of the source descriptor on (any alignment, both; wave-uniform
+// arguments): each is assembled from the two source dwords that hold its bytes
+// (the last byte at most 3 past the range's: the slack) and stored as a dword.
+__device__ __forceinline__ void copy_dwords(const __amdgpu_buffer_rsrc_t src, uint32_t s0, char *dst, int len, int lane) {
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + (uintptr_t)len;
+  const uintptr_t a0 = (d0 + 3) & ~(uintptr_t)3, a1 = d1 & ~(uintptr_t)3;   // the whole dwords: [a0, a1), none if a0 >= a1
+  if (a0 >= a1) return;
+  const int ndw = (int)((a1 - a0) >> 2);
+  const uint32_t sa0 = s0 + (uint32_t)(a0 - d0);   // the source byte of a0
+  for (int w = lane; w < ndw; w += 64) {
+    const uint32_t sa = sa0 + 4u * (uint32_t)w;
+    const v2u q = __builtin_amdgcn_raw_buffer_load_b64(src, sa & ~3u, 0, 0);
+    *reinterpret_cast<uint32_t *>(a0 + 4u * (uintptr_t)w) = __builtin_amdgcn_alignbyte(q[1], q[0], sa & 3u);
+  }
+}
+
+// The up to three bytes before and the up to three behind the whole dwords of a
+// read's output range, of both streams at once: lanes 0 .. 2 and 3 .. 5 the
+// sequence's, 6 .. 8 and 9 .. 11 the quality's.  A range that ends before its
+// first dword boundary is all "before".  Byte loads inside the read, byte
+// stores inside the range.
+__device__ __forceinline__ void copy_edges(const char *seq, const char *qual, char *seq_out, char *qual_out, int len, int lane) {
+  if (lane >= 12) return;
+  const bool q = lane >= 6;
+  const int e = q ? lane - 6 : lane;
+  const char *src = q ? qual : seq;
+  const uintptr_t d0 = reinterpret_cast<uintptr_t>(q ? qual_out : seq_out), d1 = d0 + (uintptr_t)len;
+  const uintptr_t a0 = (d0 + 3) & ~(uintptr_t)3, a1 = d1 & ~(uintptr_t)3;
+  const uintptr_t at = e < 3 ? d0 + (uintptr_t)e : (a0 > a1 ? a0 : a1) + (uintptr_t)(e - 3);
+  const bool mine = e < 3 ? at < (a0 < d1 ? a0 : d1) : at < d1;
+  if (mine) *reinterpret_cast<uint8_t *>(at) = (uint8_t)src[at - d0];
+}
+
+__global__ void __launch_bounds__(kWG) clip_copy_kernel(const char *seq, const char *qual, const int32_t *idx,
+                                                        const int32_t *idx_out, int64_t n, char *seq_out, char *qual_out) {
+  const int lane = threadIdx.x & 63;
+  // (the wave's number through an SGPR: the descriptors and offsets below stay scalar)
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const reads::Batch rs = reads::open<false>(seq, idx, n, nullptr);
+  const reads::Batch rq = reads::open<false>(qual, idx, n, nullptr);
+  const __amdgpu_buffer_rsrc_t ro = reads::idx_rsrc(idx_out, n);
+  const int64_t ngroups = (n + kGroup - 1) / kGroup;
+  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const int64_t rb = g * kGroup + wave * kR;
+    if (rb >= n) continue;
+    int32_t ix;
+    uint32_t mk;
+    reads::step_reads<kR, false>(rs, rb, n, lane, ix, mk);
+    const int64_t r = rb + lane;
+    const int32_t ox =
+        (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ro, r <= n && lane <= kR ? (uint32_t)r * 4u : reads::kNone, 0, 0);
+    for (int i = 0; i < kR; ++i) {
+      if ((uint32_t)__builtin_amdgcn_readlane((int)mk, i) != 1u) break;   // past the batch (wave-uniform)
+      const int32_t a = __builtin_amdgcn_readlane(ix, i);
+      const int32_t o = __builtin_amdgcn_readlane(ox, i);
+      const int32_t keep = __builtin_amdgcn_readlane(ox, i + 1) - o;
+      if (keep <= 0) continue;
+      copy_dwords(rs.bytes, (uint32_t)a + rs.shift, seq_out + o, keep, lane);
+      copy_dwords(rq.bytes, (uint32_t)a + rq.shift, qual_out + o, keep, lane);
+      copy_edges(seq + a, qual + a, seq_out + o, qual_out + o, keep, lane);
+    }
+  }
+}
+
+// out[i] += *carry: the running offset of the parts before this one
+__global__ void clip_carry_kernel(int32_t *out, int64_t n, const int32_t *carry) {
+  const int32_t c = *carry;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] += c;
+}
+
+}  // namespace clip
+}  // namespace hpgq
+
+struct hpgq_clip {
+  int device = 0;
+  hpgq::accum::Stream stream;
+  hpgq::accum::Retired retired;             // owned buffers replaced by larger ones
+  hpgq::clip::Probes pr;
+  bool wide = false;
+  unsigned long long *d_scal = nullptr;     // [kScalars]
+  unsigned long long *h_scal = nullptr;     // pinned: the scalars, then the two offsets hpgq_clip_batch_device fetches
+  int cus = 0, max_wg = 0;
+  char *d_tmp = nullptr;                    // the scan's temporary storage
+  size_t tmp_bytes = 0;
+  uint32_t *d_pos = nullptr;                // positions when the caller wants none: [pos_cap]
+  int64_t pos_cap = 0;
+  // hpgq_clip_batch_device's outputs
+  char *o_seq = nullptr, *o_qual = nullptr;
+  int32_t *o_idx = nullptr;
+  size_t o_bytes = 0;
+  int64_t o_reads = -1;
+
+  unsigned grid(int64_t per_cu, int64_t groups) const {
+    return (unsigned)hpgq::accum::capped(std::min<int64_t>(per_cu * (int64_t)std::max(1, cus), groups), max_wg);
+  }
+
+  // a device buffer of at least `want` units in place of *p (cap: its size now), the old one retired
+  template <class T>
+  int grow(T **p, size_t unit, size_t want, bool zero) {
+    T *d = nullptr;
+    if (hipMalloc(reinterpret_cast<void **>(&d), want * unit) != hipSuccess) return HPGQ_E_NOMEM;
+    if (zero) HPGQ_HIP_TRY(hipMemsetAsync(d, 0, want * unit, stream));
+    if (*p) retired.add(*p);
+    *p = d;
+    return HPGQ_OK;
+  }
+
+  int need_pos(int64_t n) {
+    if (n <= pos_cap) return HPGQ_OK;
+    const int64_t cap = std::max<int64_t>(n, pos_cap + pos_cap / 2);
+    const int rc = grow(&d_pos, 4, (size_t)cap, false);
+    if (rc == HPGQ_OK) pos_cap = cap;
+    return rc;
+  }
+
+  int settle() {
+    HPGQ_HIP_TRY(hipSetDevice(device));
+    HPGQ_HIP_TRY(hipMemcpyAsync(h_scal, d_scal, hpgq::clip::kScalars * 8, hipMemcpyDeviceToHost, stream));
+    HPGQ_HIP_TRY(hipStreamSynchronize(stream));
+    retired.free_all();
+    return HPGQ_OK;
+  }
+};
+
+namespace {
+
+using namespace hpgq::clip;
+
+bool batch_ok(const hpgq_batch_t *b) { return b && b->num_reads >= 0 && (b->num_reads == 0 || (b->seq && b->data_indices)); }
+
+// the find pass over b, async: positions to pos (never null), probes to probe (may be null)
+int find(hpgq_clip *q, const hpgq_batch_t *b, uint32_t *pos, uint8_t *probe) {
+  return hpgq::accum::for_parts(b, nullptr, [&](const int32_t *ix, const uint8_t *, int64_t n) {
+    const int64_t lo = ix - b->data_indices;
+    // four workgroups of 512 threads per CU stay resident (8.6 KB of LDS each)
+    const dim3 grid(q->grid(4, (n + kGroup - 1) / kGroup));
+    auto *k = q->wide ? clip_find_kernel<true> : clip_find_kernel<false>;
+    hipLaunchKernelGGL(k, grid, dim3(kWG), 0, q->stream, b->seq, ix, n, q->pr, pos + lo, probe ? probe + lo : nullptr,
+                       q->d_scal);
+  });
+}
+
+// idx_out[0] = 0, idx_out[i + 1] = idx_out[i] + pos[i], then the copy; async
+int scan_and_copy(hpgq_clip *q, const hpgq_batch_t *b, const uint32_t *pos, char *seq_out, char *qual_out,
+                  int32_t *idx_out) {
+  HPGQ_HIP_TRY(hipMemsetAsync(idx_out, 0, 4, q->stream));
+  if (b->num_reads == 0) return HPGQ_OK;
+  const int first = (int)std::min<int64_t>(b->num_reads, hpgq::accum::kPart);
+  size_t tb = 0;
+  HPGQ_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, reinterpret_cast<const int32_t *>(pos), idx_out + 1, first,
+                                                q->stream));
+  if (tb > q->tmp_bytes) {
+    const int rc = q->grow(&q->d_tmp, 1, tb, false);
+    if (rc) return rc;
+    q->tmp_bytes = tb;
+  }
+  return hpgq::accum::for_parts(b, nullptr, [&](const int32_t *ix, const uint8_t *, int64_t n) {
+    const int64_t lo = ix - b->data_indices;
+    size_t bytes = q->tmp_bytes;
+    (void)hipcub::DeviceScan::InclusiveSum(q->d_tmp, bytes, reinterpret_cast<const int32_t *>(pos + lo), idx_out + lo + 1,
+                                           (int)n, q->stream);
+    if (lo) hipLaunchKernelGGL(clip_carry_kernel, dim3(1024), dim3(256), 0, q->stream, idx_out + lo + 1, n, idx_out + lo);
+    const dim3 grid(q->grid(4, (n + kGroup - 1) / kGroup));
+    hipLaunchKernelGGL(clip_copy_kernel, grid, dim3(kWG), 0, q->stream, b->seq, b->quality, ix, idx_out + lo, n, seq_out,
+                       qual_out);
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+int hpgq_clip_open(hpgq_clip_t **cl, int device, const char *const *probes, int nprobes, int min_overlap, void *stream) {
+  if (!cl) return HPGQ_E_INVALID;
+  *cl = nullptr;
+  if (hpgq_clip_find(nullptr, 0, probes, nprobes, min_overlap, nullptr) == -2) return HPGQ_E_INVALID;   // the rules of §2.12
+  Probes pr;
+  std::memset(&pr, 0, sizeof(pr));
+  pr.n = nprobes;
+  pr.kmin = HPGQ_ADAPT_MAX_LEN;
+  pr.min_ov = min_overlap;
+  int kmax = 0;
+  for (int a = 0; a < nprobes; ++a) {
+    const int k = (int)std::strlen(probes[a]);
+    for (int j = 0; j < k; ++j) pr.code[a] |= (uint64_t)code_of((unsigned char)probes[a][j]) << (2 * j);
+    pr.len[a] = (uint32_t)k;
+    pr.kmin = std::min(pr.kmin, k);
+    kmax = std::max(kmax, k);
+  }
+  int rc = hpgq::accum::use_device(device);
+  if (rc) return rc;
+  hpgq_clip *q = new hpgq_clip;
+  q->device = device;
+  q->pr = pr;
+  q->wide = kmax > kNarrowMax;
+  rc = q->stream.open(stream);
+  if (rc == HPGQ_OK && (hipMalloc(reinterpret_cast<void **>(&q->d_scal), kScalars * 8) != hipSuccess ||
+                        hipHostMalloc(reinterpret_cast<void **>(&q->h_scal), kScalars * 8 + 8, hipHostMallocDefault) != hipSuccess))
+    rc = HPGQ_E_NOMEM;
+  if (rc == HPGQ_OK && (hipMemsetAsync(q->d_scal, 0, kScalars * 8, q->stream) != hipSuccess ||
+                        hipDeviceGetAttribute(&q->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess))
+    rc = HPGQ_E_HIP;
+  if (rc) {
+    hpgq_clip_close(q);
+    return rc;
+  }
+  *cl = q;
+  return HPGQ_OK;
+}
+
+void hpgq_clip_close(hpgq_clip_t *q) {
+  if (!q) return;
+  (void)hipSetDevice(q->device);
+  if (q->stream) (void)hipStreamSynchronize(q->stream);
+  q->retired.free_all();
+  (void)hipFree(q->d_scal);
+  (void)hipFree(q->d_tmp);
+  (void)hipFree(q->d_pos);
+  (void)hipFree(q->o_seq);
+  (void)hipFree(q->o_qual);
+  (void)hipFree(q->o_idx);
+  if (q->h_scal) (void)hipHostFree(q->h_scal);
+  q->stream.close();
+  delete q;
+}
+
+int hpgq_clip_find_device(hpgq_clip_t *q, const hpgq_batch_t *b, uint32_t *pos_out, uint8_t *probe_out) {
+  if (!q || !batch_ok(b)) return HPGQ_E_INVALID;
+  if (b->num_reads == 0) return HPGQ_OK;
+  if (!pos_out) return HPGQ_E_INVALID;
+  HPGQ_HIP_TRY(hipSetDevice(q->device));
+  return find(q, b, pos_out, probe_out);
+}
+
+int hpgq_clip_device(hpgq_clip_t *q, const hpgq_batch_t *b, char *seq_out, char *qual_out, int32_t *idx_out,
+                     uint32_t *pos_out, uint8_t *probe_out) {
+  if (!q || !batch_ok(b) || !idx_out) return HPGQ_E_INVALID;
+  if (b->num_reads && (!b->quality || !seq_out || !qual_out)) return HPGQ_E_INVALID;
+  HPGQ_HIP_TRY(hipSetDevice(q->device));
+  if (!pos_out && b->num_reads) {
+    const int rc = q->need_pos(b->num_reads);
+    if (rc) return rc;
+    pos_out = q->d_pos;
+  }
+  const int rc = b->num_reads ? find(q, b, pos_out, probe_out) : HPGQ_OK;
+  return rc ? rc : scan_and_copy(q, b, pos_out, seq_out, qual_out, idx_out);
+}
+
+int hpgq_clip_batch_device(hpgq_clip_t *q, const hpgq_batch_t *in, hpgq_batch_t *out) {
+  if (!q || !batch_ok(in) || !out || (in->num_reads && !in->quality)) return HPGQ_E_INVALID;
+  HPGQ_HIP_TRY(hipSetDevice(q->device));
+  const hpgq_batch_t b = *in;   // (in and out may be the same struct)
+  // the input's bytes: its first and last offset live on the device
+  size_t bytes = 0;
+  if (b.num_reads) {
+    int32_t *ends = reinterpret_cast<int32_t *>(q->h_scal + kScalars);
+    HPGQ_HIP_TRY(hipMemcpyAsync(ends, b.data_indices, 4, hipMemcpyDeviceToHost, q->stream));
+    HPGQ_HIP_TRY(hipMemcpyAsync(ends + 1, b.data_indices + b.num_reads, 4, hipMemcpyDeviceToHost, q->stream));
+    HPGQ_HIP_TRY(hipStreamSynchronize(q->stream));
+    if (ends[1] < ends[0]) return HPGQ_E_INVALID;
+    bytes = (size_t)(ends[1] - ends[0]);
+  }
+  if (!q->o_seq || bytes > q->o_bytes) {
+    const size_t cap = std::max(bytes, q->o_bytes + q->o_bytes / 2);
+    int rc = q->grow(&q->o_seq, 1, cap + HPGQ_DEVICE_SLACK, true);
+    if (rc == HPGQ_OK) rc = q->grow(&q->o_qual, 1, cap + HPGQ_DEVICE_SLACK, true);
+    if (rc) return rc;
+    q->o_bytes = cap;
+  }
+  if (b.num_reads > q->o_reads) {
+    const int64_t cap = std::max<int64_t>(b.num_reads, q->o_reads + q->o_reads / 2);
+    const int rc = q->grow(&q->o_idx, 4, (size_t)cap + 1, false);
+    if (rc) return rc;
+    q->o_reads = cap;
+  }
+  const int rc = hpgq_clip_device(q, &b, q->o_seq, q->o_qual, q->o_idx, nullptr, nullptr);
+  if (rc) return rc;
+  out->num_reads = b.num_reads;
+  out->seq = q->o_seq;
+  out->quality = q->o_qual;
+  out->data_indices = q->o_idx;
+  return HPGQ_OK;
+}
+
+int hpgq_clip_sync(hpgq_clip_t *q) { return q ? q->settle() : HPGQ_E_INVALID; }
+
+int hpgq_clip_reset(hpgq_clip_t *q) {
+  if (!q) return HPGQ_E_INVALID;
+  HPGQ_HIP_TRY(hipSetDevice(q->device));
+  HPGQ_HIP_TRY(hipMemsetAsync(q->d_scal, 0, kScalars * 8, q->stream));
+  return HPGQ_OK;
+}
+
+int hpgq_clip_read(hpgq_clip_t *q, hpgq_clip_info_t *info) {
+  if (!q || !info) return HPGQ_E_INVALID;
+  const int rc = q->settle();
+  if (rc) return rc;
+  info->reads = q->h_scal[0];
+  info->clipped = q->h_scal[1];
+  info->bases_removed = q->h_scal[2];
+  for (int a = 0; a < kMaxProbes; ++a) info->by_probe[a] = q->h_scal[3 + a];
+  info->nprobes = q->pr.n;
+  info->min_overlap = q->pr.min_ov;
+  return HPGQ_OK;
+}
+
+int hpgq_clip_debug_set_max_workgroups(hpgq_clip_t *q, int max_wg) {
+  if (!q || max_wg < 0) return HPGQ_E_INVALID;
+  q->max_wg = max_wg;
+  return HPGQ_OK;
+}
+
+}  // extern "C"

@@ -38,7 +38,7 @@ int main(int argc, char **argv) {
   cli_options_t *o = cli_parse(cmd, exec_name, argc - 1, argv + 1);
   hpgq_params_t p;
   cli_params(o, &p);
-  if (o->adapters_on && cli_adapters_load(o)) {   /* (one line on stderr; before any GPU work) */
+  if ((o->adapters_on || o->clip_on) && cli_adapters_load(o)) {   /* (one line on stderr; before any GPU work) */
     cli_free(o);
     return 1;
   }
@@ -147,6 +147,12 @@ int main(int argc, char **argv) {
                                        r.adapt_with_any[m], p.paired ? mate_name[m] : cli_base_name(o->in_filename)))
       rc = 1;
   }
+  /* --clip-adapters: one file per mate, named as that mate's report set would be */
+  for (int m = 0; r.clip_on && m < (p.paired ? 2 : 1); ++m) {
+    const char *names[HPGQ_ADAPT_MAX_PROBES];
+    for (int a = 0; a < o->adapter_n; ++a) names[a] = o->adapter_names[a];
+    if (cli_report_clip(o, o->adapter_n, names, &r.clip[m], p.paired ? mate_name[m] : cli_base_name(o->in_filename))) rc = 1;
+  }
 
   if (!o->quiet) {
     printf("\n\nRESULTS\n");
@@ -165,6 +171,7 @@ int main(int argc, char **argv) {
     } else if (p.paired) {
       const char *ok = cmd == CMD_FILTER ? "passed" : "edit";
       if (cmd == CMD_EDIT) printf("Num. edited reads : %lu (mate 1)\n", (unsigned long)r.num_edited);
+      if (r.clip_on) printf("Num. clipped reads : %lu (mate 1)\n", (unsigned long)r.clip[0].clipped);
       printf("Num. passed pairs : %lu (%s/%s_1.fq, %s/%s_2.fq)\n", (unsigned long)r.num_passed, o->out_dirname, ok,
              o->out_dirname, ok);
       if (p.filter_on)
@@ -175,6 +182,7 @@ int main(int argc, char **argv) {
       printf("Num. failed reads: %lu (%s/failed.fq)\n", (unsigned long)r.num_failed, o->out_dirname);
     } else {
       printf("Num. edited reads : %lu\n", (unsigned long)r.num_edited);
+      if (r.clip_on) printf("Num. clipped reads : %lu\n", (unsigned long)r.clip[0].clipped);
       printf("Output file       : %s/edit.fq\n", o->out_dirname);
       if (p.filter_on) {
         printf("\nFiltering : Enabled\n");

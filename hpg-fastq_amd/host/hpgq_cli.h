@@ -46,6 +46,8 @@ typedef struct {
   int adapter_n;            /* the probe set in order (cli_adapters_load): 1 .. HPGQ_ADAPT_MAX_PROBES */
   char adapter_names[HPGQ_ADAPT_MAX_PROBES][CLI_ADAPTER_NAME_MAX + 1];
   char adapter_probes[HPGQ_ADAPT_MAX_PROBES][HPGQ_ADAPT_MAX_LEN + 1];
+  int clip_on;              /* edit --clip-adapters: the set above, from --clip-adapter-file or the default */
+  int clip_min_overlap;     /* --clip-min-overlap: 1 .. HPGQ_ADAPT_MAX_LEN */
   /* chaos game (old/main_hpg_fastq_old.c:185-189: --cg | --chaos-game, --k, --gs-filename) */
   int cg_on, k_cg;
   char *gs_filename;
@@ -114,6 +116,8 @@ typedef struct {
   uint64_t *adapt[2];
   int adapt_npos[2];
   uint64_t adapt_reads[2], adapt_with_any[2];
+  int clip_on;              /* --clip-adapters: clip[] hold the mates' scalars, the workers' added */
+  hpgq_clip_info_t clip[2];
   uint32_t *cg_seq, *cg_q;  /* --cg: table_seq / table_q [dim*dim] (malloc'd) */
   uint32_t cg_words;        /* fq_word_count */
   int cg_exact_calls;       /* chaos-game calls the exact simulation redid */
@@ -142,13 +146,16 @@ int cli_report_dup(const cli_options_t *o, const hpgq_dup_levels_t *lv, const ch
 /* --overrepresented: <base>.overrepresented.data, n sequences in rank order */
 int cli_report_overrep(const cli_options_t *o, size_t n, const uint64_t *counts, const uint64_t *lens,
                        unsigned char *const *seqs, uint64_t reads, const char *base);
-/* --adapters: the probe set into o->adapter_n / _names / _probes, from
- * --adapter-file or the default set; on a violation one line on stderr and -1.
- * No device. */
+/* --adapters / --clip-adapters: the probe set into o->adapter_n / _names /
+ * _probes, from --adapter-file / --clip-adapter-file or the default set; on a
+ * violation one line on stderr and -1.  No device. */
 int cli_adapters_load(cli_options_t *o);
 /* --adapters: <base>.adapter.content.data from one mate's table first[nprobes][npos] */
 int cli_report_adapt(const cli_options_t *o, int nprobes, const char *const *names, const uint64_t *first, int npos,
                      uint64_t reads, uint64_t with_any, const char *base);
+/* --clip-adapters: <base>.adapter.clip.data from one mate's scalars */
+int cli_report_clip(const cli_options_t *o, int nprobes, const char *const *names, const hpgq_clip_info_t *info,
+                    const char *base);
 const char *cli_base_name(const char *path);
 /* the report base names of the two mates: each input's base name, or
  * <base>_1 / <base>_2 for --interleaved (out: 2 x 4096 bytes) */

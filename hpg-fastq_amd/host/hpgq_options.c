@@ -9,7 +9,8 @@
  * --counters-out, --kmers-out, --quiet, and stats --quality-dist /
  * --quality-dist-out, --overrepresented and its value flags
  *  and --duplication / --duplication-out
- * (§2.9), --adapters / --adapter-file / --adapters-out (§2.11).
+ * (§2.9), --adapters / --adapter-file / --adapters-out (§2.11), --clip-adapters /
+ * --clip-adapter-file / --clip-min-overlap (§2.12).
  * --quality-encoding is accepted by every command
  * (quirk Q11).
  */
@@ -96,6 +97,11 @@ static void usage(const cli_options_t *o) {
     printf("  --gs-filename=<file>            Reference genomic signature: difference table and image\n");
     printf("  --cg-batch-size=<int>           FastQ text bytes per chaos-game call (default 64000000)\n");
   }
+  if (o->command == CMD_EDIT) {
+    printf("  --clip-adapters                 Cut every read at its first adapter, before the trim and the filter\n");
+    printf("  --clip-adapter-file=<file>      Probes instead of the default set: lines of name, tab(s), sequence\n");
+    printf("  --clip-min-overlap=<int>        Bases of an adapter a read must end in to be cut there (1-32, default 8)\n");
+  }
   printf("  --read-length-range=<string>    Read length range, eg. 80,110\n");
   printf("  --read-quality-range=<string>   Read quality range, eg. 20,40\n");
   printf("  --left-length=<int>             Number of leftmost nucleotides to take into account to %s\n",
@@ -157,7 +163,7 @@ enum {
   O_RQRANGE, O_MAXN, O_MAXOOQ, O_GPU, O_LMAX, O_CHUNK, O_PRINT, O_COUNTERS, O_QUIET,
   O_KMERSOUT, O_CG, O_KCG, O_GS, O_GPUS, O_CGBATCH, O_CGOUT, O_GPUW, O_STREAMW, O_WHOOK, O_COPYT, O_PFT,
   O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT, O_DUP, O_DUPOUT, O_OVER, O_OVERMIN, O_OVERTOP, O_OVERBYTES,
-  O_ADAPT, O_ADAPTFILE, O_ADAPTOUT
+  O_ADAPT, O_ADAPTFILE, O_ADAPTOUT, O_CLIP, O_CLIPFILE, O_CLIPOV
 };
 
 /* a whole-string decimal in [lo, hi] (u64), else the usage error */
@@ -196,6 +202,8 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   o->overrep_bytes = (uint64_t)1 << 28;
   int overrep_values = 0;   /* a value flag of --overrepresented was given */
   int adapter_values = 0;   /* --adapter-file or --adapters-out was given */
+  int clip_values = 0;      /* --clip-adapter-file or --clip-min-overlap was given */
+  o->clip_min_overlap = HPGQ_ADAPT_MIN_LEN;
   static const struct option longopts[] = {
       {"help", no_argument, 0, 'h'},
       {"fastq-file", required_argument, 0, 'f'},
@@ -242,6 +250,9 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
       {"adapters", no_argument, 0, O_ADAPT},
       {"adapter-file", required_argument, 0, O_ADAPTFILE},
       {"adapters-out", required_argument, 0, O_ADAPTOUT},
+      {"clip-adapters", no_argument, 0, O_CLIP},
+      {"clip-adapter-file", required_argument, 0, O_CLIPFILE},
+      {"clip-min-overlap", required_argument, 0, O_CLIPOV},
       {"quiet", no_argument, 0, O_QUIET},
       {"stream-writer", no_argument, 0, O_STREAMW},
       {"writer-test-hook", required_argument, 0, O_WHOOK},
@@ -317,6 +328,21 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
           o->adapters_out = strdup(optarg);
         }
         break;
+      case O_CLIP:
+      case O_CLIPFILE:
+      case O_CLIPOV:
+        if (command != CMD_EDIT) {   /* one line, before anything is opened or written */
+          fprintf(stderr, "hpg-fastq: --clip-adapters is an option of the edit command, not of %s\n", o->command_name);
+          exit(1);
+        }
+        if (c == O_CLIP) o->clip_on = 1;
+        else clip_values = 1;
+        if (c == O_CLIPFILE) {   /* (edit has no --adapter-file: the set's file is this one) */
+          free(o->adapter_file);
+          o->adapter_file = strdup(optarg);
+        }
+        if (c == O_CLIPOV) o->clip_min_overlap = count_arg(o, "clip-min-overlap", optarg, 1, HPGQ_ADAPT_MAX_LEN);
+        break;
       case O_CG:
         if (command != CMD_STATS) usage(o);
         o->cg_on = 1;
@@ -374,6 +400,10 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   }
   if (adapter_values && !o->adapters_on) {
     printf("\nError: --adapter-file and --adapters-out need --adapters\n");
+    usage(o);
+  }
+  if (clip_values && !o->clip_on) {
+    printf("\nError: --clip-adapter-file and --clip-min-overlap need --clip-adapters\n");
     usage(o);
   }
   if (fq1) o->in_filename = fq1;
@@ -496,6 +526,8 @@ void cli_display(const cli_options_t *o) {
            (unsigned long)o->overrep_min_count);
   if (o->adapters_on)
     printf("\tAdapter content      : %d probes, first occurrence per read (--adapters)\n", o->adapter_n);
+  if (o->clip_on)
+    printf("\tAdapter clipping     : %d probes, min overlap %d (--clip-adapters)\n", o->adapter_n, o->clip_min_overlap);
   printf("\n%s options\n", o->command == CMD_EDIT ? "Edit and filter" : "Filter");
   int shown = 0;
   if (o->read_length_range) printf("\tRead length range   : %s\n", o->read_length_range), shown++;

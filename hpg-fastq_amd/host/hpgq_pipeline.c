@@ -813,6 +813,7 @@ typedef struct {
   hpgq_qdist_t *qd[2];    /* --quality-dist: one table per mate, on the ctx stream */
   hpgq_dup_t *dp[2];      /* --duplication: one hash table per mate, on the ctx stream */
   hpgq_adapt_t *ad[2];    /* --adapters: one table per mate, on the ctx stream */
+  hpgq_clip_t *cl[2];     /* --clip-adapters: one handle per mate, on the ctx stream */
   hpgq_cgr_t *cg;
   uint8_t *d_mask;
   uint32_t *d_trim;
@@ -841,6 +842,12 @@ static int worker_open(worker_t *W) {
     for (int a = 0; a < o->adapter_n; ++a) probes[a] = o->adapter_probes[a];
     rc = hpgq_adapt_open(&W->ad[m], W->device, probes, o->adapter_n, W->p->lmax, hpgq_stream(W->ctx));
   }
+  /* --clip-adapters cuts each mate on its own before the engine sees it */
+  for (int m = 0; m < W->P->nmates && rc == 0 && o->clip_on; ++m) {
+    const char *probes[HPGQ_ADAPT_MAX_PROBES];
+    for (int a = 0; a < o->adapter_n; ++a) probes[a] = o->adapter_probes[a];
+    rc = hpgq_clip_open(&W->cl[m], W->device, probes, o->adapter_n, o->clip_min_overlap, hpgq_stream(W->ctx));
+  }
   /* --duplication counts the same reads again, per mate, by their sequence;
    * --overrepresented needs the same tables, keeping the bytes of the sequences
    * that reach ceil(K / workers) in one of them: a sequence with K or more in
@@ -868,6 +875,8 @@ static void worker_close(worker_t *W) {
   hpgq_qdist_close(W->qd[1]);
   hpgq_adapt_close(W->ad[0]);
   hpgq_adapt_close(W->ad[1]);
+  hpgq_clip_close(W->cl[0]);
+  hpgq_clip_close(W->cl[1]);
   hpgq_dup_close(W->dp[0]);
   hpgq_dup_close(W->dp[1]);
   hpgq_cgr_close(W->cg);
@@ -959,6 +968,10 @@ static int worker_chunk(worker_t *W, slot_t *s) {
     }
   }
   if (rc || b[0].num_reads == 0) return rc;
+  /* --clip-adapters: from here on the batch is the kept reads, in buffers the
+   * handle owns until its next chunk (this chunk's hpgq_sync comes before that) */
+  for (int m = 0; m < nm && W->cl[m]; ++m)
+    if ((rc = hpgq_clip_batch_device(W->cl[m], &b[m], &b[m])) != 0) return rc;
   const size_t n = (size_t)b[0].num_reads;
   if (need_mask && n > W->dcap) {
     hpgq_device_free(W->d_mask);
@@ -1264,6 +1277,21 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
       if (rc == 0) rc = hpgq_qdist_add(res->qdist[m], np, part, pw);
     }
     free(part);
+  }
+  /* --clip-adapters: per mate, the workers' scalars added */
+  for (int m = 0; m < nm && rc == 0 && o->clip_on; ++m) {
+    res->clip_on = 1;
+    for (int w = 0; w < G && rc == 0; ++w) {
+      hpgq_clip_info_t info;
+      rc = hpgq_clip_read(W[w].cl[m], &info);
+      if (rc) break;
+      res->clip[m].reads += info.reads;
+      res->clip[m].clipped += info.clipped;
+      res->clip[m].bases_removed += info.bases_removed;
+      for (int a = 0; a < HPGQ_ADAPT_MAX_PROBES; ++a) res->clip[m].by_probe[a] += info.by_probe[a];
+      res->clip[m].nprobes = info.nprobes;
+      res->clip[m].min_overlap = info.min_overlap;
+    }
   }
   /* --adapters: per mate, the workers' tables added at the longest worker's
    * positions (hpgq_adapt_add), and the two scalars added */

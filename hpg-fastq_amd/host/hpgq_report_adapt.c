@@ -3,7 +3,8 @@
  * (build-defined; the reference has nothing like it).
  *
  * cli_adapters_load: the set a run counts, from --adapter-file (lines of name,
- * tab(s), sequence) or libhpgq's default set.
+ * tab(s), sequence) or libhpgq's default set; `edit --clip-adapters` takes its
+ * set through it too, from --clip-adapter-file.
  *
  * <in>.adapter.content.data: the counted reads and those with any probe, then
  * per position p = 1 .. npos and probe the percentage of the counted reads in
@@ -17,13 +18,16 @@
 
 #include "hpgq_cli.h"
 
+static const char *file_flag = "--adapter-file";   /* the flag the file came with (cli_adapters_load sets it) */
+
 static int file_error(const char *path, long line, const char *what) {
-  fprintf(stderr, "hpg-fastq: --adapter-file: %s:%ld: %s\n", path, line, what);
+  fprintf(stderr, "hpg-fastq: %s: %s:%ld: %s\n", file_flag, path, line, what);
   return -1;
 }
 
 int cli_adapters_load(cli_options_t *o) {
   o->adapter_n = 0;
+  file_flag = o->clip_on ? "--clip-adapter-file" : "--adapter-file";
   if (!o->adapter_file) {
     const int n = hpgq_adapt_default(-1, NULL, NULL);
     for (int i = 0; i < n && i < HPGQ_ADAPT_MAX_PROBES; ++i) {

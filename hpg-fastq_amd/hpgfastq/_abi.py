@@ -100,6 +100,11 @@ class AdaptInfo(C.Structure):
     _fields_ = [("reads", C.c_uint64), ("with_any", C.c_uint64), ("nprobes", C.c_int32), ("npos", C.c_int32)]
 
 
+class ClipInfo(C.Structure):
+    _fields_ = [("reads", C.c_uint64), ("clipped", C.c_uint64), ("bases_removed", C.c_uint64),
+                ("by_probe", C.c_uint64 * ADAPT_MAX_PROBES), ("nprobes", C.c_int32), ("min_overlap", C.c_int32)]
+
+
 class GsInfo(C.Structure):
     _fields_ = [("words", C.c_uint64), ("bases", C.c_uint64), ("ns", C.c_uint64),
                 ("sequences", C.c_uint64)]
@@ -235,6 +240,17 @@ _SIGS = [
     ("hpgq_adapt_add", C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     ("hpgq_adapt_find", C.c_int64, [C.c_char_p, C.c_size_t, C.c_char_p]),
     ("hpgq_adapt_default", C.c_int, [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p)]),
+    ("hpgq_clip_open", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_void_p]),
+    ("hpgq_clip_close", None, [C.c_void_p]),
+    ("hpgq_clip_find_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p]),
+    ("hpgq_clip_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
+    ("hpgq_clip_batch_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Batch)]),
+    ("hpgq_clip_sync", C.c_int, [C.c_void_p]),
+    ("hpgq_clip_reset", C.c_int, [C.c_void_p]),
+    ("hpgq_clip_read", C.c_int, [C.c_void_p, C.POINTER(ClipInfo)]),
+    ("hpgq_clip_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
+    ("hpgq_clip_find", C.c_int64, [C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(C.c_int)]),
     ("hpgq_synth_length", C.c_int32, [C.POINTER(Synth), C.c_int64]),
     ("hpgq_synth_indices_host", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p]),
     ("hpgq_synth_device", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p,

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, AdaptInfo, counters_len,
+from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, AdaptInfo, ClipInfo, counters_len,
                    CGR_ALL_READS, ROUTES, E_PAIRING, QDIST_VALUES, DUP_LEVELS, HpgqError)
 
 # Kernel route for new Engines (tests / A/B: a key of ROUTES, or None for the
@@ -456,6 +456,62 @@ def adapt_defaults():
         lib.hpgq_adapt_default(i, C.byref(name), C.byref(probe))
         out.append((name.value, probe.value))
     return out
+
+
+def _probe_array(probes):
+    if probes is None:
+        probes = [p for _, p in adapt_defaults()]
+    probes = [p.encode() if isinstance(p, str) else bytes(p) for p in probes]
+    return probes, (C.c_char_p * max(len(probes), 1))(*probes)
+
+
+class AdapterClip(_Handle):
+    """hpgq_clip: `edit --clip-adapters`, every read cut at the lowest position at
+    which a probe matches, whole or running off the read's end by at least
+    `min_overlap` bases.  `probes` as AdapterContent's (None:
+    the default set).  All pointers are device pointers (ints)."""
+
+    _prefix = "hpgq_clip"
+
+    def __init__(self, probes=None, min_overlap=8, device=0, stream=None):
+        self.probes, arr = _probe_array(probes)
+        self.min_overlap = int(min_overlap)
+        self._open(device, arr, len(self.probes), self.min_overlap, stream)
+
+    def find(self, batch, pos_ptr, probe_ptr=None):
+        """hpgq_clip_find_device: pos u32 [n] and, unless None, probe u8 [n] (async)."""
+        self._call("find_device", C.byref(batch), pos_ptr, probe_ptr)
+
+    def clip_device(self, batch, seq_ptr, qual_ptr, idx_ptr, pos_ptr=None, probe_ptr=None):
+        """hpgq_clip_device: the kept reads into the caller's buffers (async)."""
+        self._call("device", C.byref(batch), seq_ptr, qual_ptr, idx_ptr, pos_ptr, probe_ptr)
+
+    def clip_batch(self, batch):
+        """hpgq_clip_batch_device: the kept reads as a Batch over buffers the
+        handle owns, valid until the next clip_batch or close."""
+        out = Batch()
+        self._call("batch_device", C.byref(batch), C.byref(out))
+        return out
+
+    def info(self):
+        """dict(reads, clipped, bases_removed, by_probe [nprobes], nprobes, min_overlap); synchronises."""
+        i = ClipInfo()
+        self._call("read", C.byref(i))
+        return dict(reads=int(i.reads), clipped=int(i.clipped), bases_removed=int(i.bases_removed),
+                    by_probe=[int(x) for x in i.by_probe[:i.nprobes]], nprobes=int(i.nprobes),
+                    min_overlap=int(i.min_overlap))
+
+
+def clip_find(s, probes=None, min_overlap=8):
+    """hpgq_clip_find: (c, winning probe or -1) of the bytes s (HpgqError -1 for
+    a set or a min_overlap that breaks the rules)."""
+    s = bytes(s)
+    probes, arr = _probe_array(probes)
+    who = C.c_int(-1)
+    c = lib.hpgq_clip_find(s, len(s), arr, len(probes), int(min_overlap), C.byref(who))
+    if c == -2:
+        raise HpgqError(-1, "hpgq_clip_find")
+    return int(c), int(who.value)
 
 
 def _levels_dict(lv):

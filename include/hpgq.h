@@ -771,6 +771,68 @@ int64_t hpgq_adapt_find(const void *s, size_t n, const char *probe);
 int  hpgq_adapt_default(int i, const char **name, const char **probe);
 
 /* ---------------------------------------------------------------------- */
+/* edit --clip-adapters: cut reads at the adapter                           */
+/* ---------------------------------------------------------------------- */
+
+/*
+ * Build-defined.  The probes are those of hpgq_adapt (same
+ * rules, same default set); min_overlap is 1 .. HPGQ_ADAPT_MAX_LEN (the CLI's
+ * default: HPGQ_ADAPT_MIN_LEN).  Probe a of K bytes matches at position j of a
+ * read of n bytes iff, with m = min(K, n - j), the read's bytes [j, j + m)
+ * equal the probe's first m as they stand and m == K (a whole occurrence) or
+ * m >= min_overlap (the read ends inside the adapter).  N, lower case and every
+ * other byte value never match, and nothing behind the read's last byte counts.
+ * c is the lowest j at which any probe matches, n if none does; the kept read
+ * is bytes [0, c) of sequence and quality (c == 0: an empty read); the winner
+ * is the lowest probe that matches at c (0xFF when c == n).  The scalars are
+ * plain u64 sums over every batch since open or reset.
+ *
+ * Input as hpgq_adapt_count_device: device pointers, seq and quality readable
+ * HPGQ_DEVICE_SLACK bytes past the data end, any alignment, absolute offsets,
+ * reads of any length, 0 included, and an empty batch.  The inputs are never
+ * written.  Everything runs on the handle's stream.
+ */
+typedef struct hpgq_clip hpgq_clip_t;
+typedef struct hpgq_clip_info {
+  uint64_t reads, clipped, bases_removed, by_probe[HPGQ_ADAPT_MAX_PROBES];
+  int32_t nprobes, min_overlap;
+} hpgq_clip_info_t;
+
+/* probes: nprobes NUL-terminated strings, copied; stream: as hpgq_kmers_open.
+ * HPGQ_E_INVALID before any device call. */
+int  hpgq_clip_open(hpgq_clip_t **cl, int device, const char *const *probes, int nprobes,
+                    int min_overlap, void *stream);
+void hpgq_clip_close(hpgq_clip_t *cl);
+/* positions only (async): pos_out[i] = c, probe_out[i] = the winner; device
+ * pointers of num_reads elements; probe_out may be NULL */
+int  hpgq_clip_find_device(hpgq_clip_t *cl, const hpgq_batch_t *in,
+                           uint32_t *pos_out, uint8_t *probe_out);
+/* find, then the kept reads back to back into the CALLER's device buffers
+ * (async): seq_out / qual_out hold at least the input's bytes, idx_out
+ * num_reads + 1 offsets from 0; pos_out / probe_out may be NULL.  Nothing is
+ * written behind idx_out[num_reads] bytes of either output. */
+int  hpgq_clip_device(hpgq_clip_t *cl, const hpgq_batch_t *in, char *seq_out, char *qual_out,
+                      int32_t *idx_out, uint32_t *pos_out, uint8_t *probe_out);
+/* The same into buffers the handle owns (grown as needed, HPGQ_DEVICE_SLACK
+ * readable bytes behind the data).  *out is valid until the next
+ * hpgq_clip_batch_device on this handle or its close; in and out may be the
+ * same struct.  Waits for the stream once (the input's size is on the device);
+ * the clip itself is async. */
+int  hpgq_clip_batch_device(hpgq_clip_t *cl, const hpgq_batch_t *in, hpgq_batch_t *out);
+int  hpgq_clip_sync(hpgq_clip_t *cl);
+/* zero the scalars (async); the probes stay */
+int  hpgq_clip_reset(hpgq_clip_t *cl);
+/* the scalars since open or reset.  Synchronises. */
+int  hpgq_clip_read(hpgq_clip_t *cl, hpgq_clip_info_t *info);
+/* Tests only: at most max_wg workgroups per kernel (0, the default: no limit). */
+int  hpgq_clip_debug_set_max_workgroups(hpgq_clip_t *cl, int max_wg);
+/* Host only, no device (csrc/hpgq_clip_post.cpp): the rule above on one read.
+ * Returns c (n: no match) and sets *probe (may be NULL) to the winner or -1;
+ * -2 for a set or a min_overlap that breaks the rules. */
+int64_t hpgq_clip_find(const void *s, size_t n, const char *const *probes, int nprobes,
+                       int min_overlap, int *probe);
+
+/* ---------------------------------------------------------------------- */
 /* FASTQ text -> device batch (the parsing half of the producer's          */
 /* fastq_fread_se, src/stats_fastq.c:183, moved onto the GPU)              */
 /* ---------------------------------------------------------------------- */
