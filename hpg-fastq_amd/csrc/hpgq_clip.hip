@@ -32,17 +32,10 @@
 //     hit gets one more load of its last 7 bytes; lane a compares probe a, one
 //     ballot per start.
 //
-// Copy.  Read-major, kR reads per wave step.  Source and destination have any
-// byte alignment, and reads of 0 .. 3 kept bases make several reads share one
-// output dword, so no partial dword is ever read, modified and written: the
-// dwords that lie whole inside a read's output range are assembled with
-// v_alignbyte from two source dwords and stored as dwords; the up to three bytes
-// before and after them are stored as bytes.  Every store is a vector store
-// inside [idx_out[i], idx_out[i + 1]) of its read.
+// Scan and copy: hpgq_cut.h, shared with hpgq_ovl.hip.
 #include "hpgq_accum.h"
+#include "hpgq_cut.h"
 #include "hpgq_reads.h"
-
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstring>
@@ -61,6 +54,8 @@ constexpr int kPrefix = 8;            // bases of the prefilter: HPGQ_ADAPT_MIN_
 constexpr int kBitmapWords = 65536 / 32;   // one bit per 8-base prefix (16 code bits)
 constexpr int kScalars = 3 + kMaxProbes;   // reads, clipped, bases_removed, by_probe[32]
 using reads::v2u;
+using reads::pack4;
+using reads::lane_bytes;
 static_assert(kR % kPre == 0, "the reads of a wave step go in blocks of kPre");
 static_assert(kPrefix == HPGQ_ADAPT_MIN_LEN, "every probe has the prefilter's bases");
 
@@ -76,25 +71,6 @@ __host__ __device__ inline uint32_t code_of(uint32_t b) { return (b >> 1) & 3u; 
 
 __device__ __forceinline__ uint32_t pull(uint32_t v, int lane, int d) {
   return (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + d) & 63) * 4, (int)v);
-}
-
-// The lane's four bytes v (those past the read's end zeroed) as four 2-bit
-// codes c (base j at bits 2j .. 2j + 1) and four validity bits ok (base j at bit
-// j): the byte is exactly the one base with its code.
-__device__ __forceinline__ void pack4(uint32_t v, uint32_t &c, uint32_t &ok) {
-  const uint32_t x = v >> 1 & 0x03030303u;
-  const uint32_t isT = x >> 1 & ~x & 0x01010101u;
-  const uint32_t d = v ^ (0x41414141u + 2u * x + 15u * isT);
-  const uint32_t z = ~(((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
-  c = (x | x >> 6 | x >> 12 | x >> 18) & 0xFFu;
-  ok = (z >> 7 | z >> 14 | z >> 21 | z >> 28) & 0xFu;
-}
-
-// the lane's bytes st + 4 lane .. + 3 of a read with rem bytes from st on
-__device__ __forceinline__ uint32_t lane_bytes(v2u w, uint32_t st, int rem, int lane) {
-  const int nb = rem - 4 * lane;
-  const uint32_t raw = __builtin_amdgcn_alignbyte(w[1], w[0], st & 3u);
-  return nb >= 4 ? raw : nb <= 0 ? 0u : raw & ((1u << (8 * nb)) - 1u);
 }
 
 // One read of len bytes at st0 (from the descriptor's base); w0: its first
@@ -296,77 +272,6 @@ __global__ void __launch_bounds__(kWG) clip_find_kernel(const char *seq, const i
   }
 }
 
-// The dwords that lie whole inside the output range [dst, dst + len) of one
-// read, from s0 of the source descriptor on (any alignment, both; wave-uniform
-// arguments): each is assembled from the two source dwords that hold its bytes
-// (the last byte at most 3 past the range's: the slack) and stored as a dword.
-__device__ __forceinline__ void copy_dwords(const __amdgpu_buffer_rsrc_t src, uint32_t s0, char *dst, int len, int lane) {
-  const uintptr_t d0 = reinterpret_cast<uintptr_t>(dst), d1 = d0 + (uintptr_t)len;
-  const uintptr_t a0 = (d0 + 3) & ~(uintptr_t)3, a1 = d1 & ~(uintptr_t)3;   // the whole dwords: [a0, a1), none if a0 >= a1
-  if (a0 >= a1) return;
-  const int ndw = (int)((a1 - a0) >> 2);
-  const uint32_t sa0 = s0 + (uint32_t)(a0 - d0);   // the source byte of a0
-  for (int w = lane; w < ndw; w += 64) {
-    const uint32_t sa = sa0 + 4u * (uint32_t)w;
-    const v2u q = __builtin_amdgcn_raw_buffer_load_b64(src, sa & ~3u, 0, 0);
-    *reinterpret_cast<uint32_t *>(a0 + 4u * (uintptr_t)w) = __builtin_amdgcn_alignbyte(q[1], q[0], sa & 3u);
-  }
-}
-
-// The up to three bytes before and the up to three behind the whole dwords of a
-// read's output range, of both streams at once: lanes 0 .. 2 and 3 .. 5 the
-// sequence's, 6 .. 8 and 9 .. 11 the quality's.  A range that ends before its
-// first dword boundary is all "before".  Byte loads inside the read, byte
-// stores inside the range.
-__device__ __forceinline__ void copy_edges(const char *seq, const char *qual, char *seq_out, char *qual_out, int len, int lane) {
-  if (lane >= 12) return;
-  const bool q = lane >= 6;
-  const int e = q ? lane - 6 : lane;
-  const char *src = q ? qual : seq;
-  const uintptr_t d0 = reinterpret_cast<uintptr_t>(q ? qual_out : seq_out), d1 = d0 + (uintptr_t)len;
-  const uintptr_t a0 = (d0 + 3) & ~(uintptr_t)3, a1 = d1 & ~(uintptr_t)3;
-  const uintptr_t at = e < 3 ? d0 + (uintptr_t)e : (a0 > a1 ? a0 : a1) + (uintptr_t)(e - 3);
-  const bool mine = e < 3 ? at < (a0 < d1 ? a0 : d1) : at < d1;
-  if (mine) *reinterpret_cast<uint8_t *>(at) = (uint8_t)src[at - d0];
-}
-
-__global__ void __launch_bounds__(kWG) clip_copy_kernel(const char *seq, const char *qual, const int32_t *idx,
-                                                        const int32_t *idx_out, int64_t n, char *seq_out, char *qual_out) {
-  const int lane = threadIdx.x & 63;
-  // (the wave's number through an SGPR: the descriptors and offsets below stay scalar)
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const reads::Batch rs = reads::open<false>(seq, idx, n, nullptr);
-  const reads::Batch rq = reads::open<false>(qual, idx, n, nullptr);
-  const __amdgpu_buffer_rsrc_t ro = reads::idx_rsrc(idx_out, n);
-  const int64_t ngroups = (n + kGroup - 1) / kGroup;
-  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
-    const int64_t rb = g * kGroup + wave * kR;
-    if (rb >= n) continue;
-    int32_t ix;
-    uint32_t mk;
-    reads::step_reads<kR, false>(rs, rb, n, lane, ix, mk);
-    const int64_t r = rb + lane;
-    const int32_t ox =
-        (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ro, r <= n && lane <= kR ? (uint32_t)r * 4u : reads::kNone, 0, 0);
-    for (int i = 0; i < kR; ++i) {
-      if ((uint32_t)__builtin_amdgcn_readlane((int)mk, i) != 1u) break;   // past the batch (wave-uniform)
-      const int32_t a = __builtin_amdgcn_readlane(ix, i);
-      const int32_t o = __builtin_amdgcn_readlane(ox, i);
-      const int32_t keep = __builtin_amdgcn_readlane(ox, i + 1) - o;
-      if (keep <= 0) continue;
-      copy_dwords(rs.bytes, (uint32_t)a + rs.shift, seq_out + o, keep, lane);
-      copy_dwords(rq.bytes, (uint32_t)a + rq.shift, qual_out + o, keep, lane);
-      copy_edges(seq + a, qual + a, seq_out + o, qual_out + o, keep, lane);
-    }
-  }
-}
-
-// out[i] += *carry: the running offset of the parts before this one
-__global__ void clip_carry_kernel(int32_t *out, int64_t n, const int32_t *carry) {
-  const int32_t c = *carry;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] += c;
-}
-
 }  // namespace clip
 }  // namespace hpgq
 
@@ -379,38 +284,11 @@ struct hpgq_clip {
   unsigned long long *d_scal = nullptr;     // [kScalars]
   unsigned long long *h_scal = nullptr;     // pinned: the scalars, then the two offsets hpgq_clip_batch_device fetches
   int cus = 0, max_wg = 0;
-  char *d_tmp = nullptr;                    // the scan's temporary storage
-  size_t tmp_bytes = 0;
-  uint32_t *d_pos = nullptr;                // positions when the caller wants none: [pos_cap]
-  int64_t pos_cap = 0;
-  // hpgq_clip_batch_device's outputs
-  char *o_seq = nullptr, *o_qual = nullptr;
-  int32_t *o_idx = nullptr;
-  size_t o_bytes = 0;
-  int64_t o_reads = -1;
+  hpgq::cut::Scan scan;                     // the scan's temporary storage
+  hpgq::cut::Positions pos;                 // positions when the caller wants none
+  hpgq::cut::Kept kept;                     // hpgq_clip_batch_device's outputs
 
-  unsigned grid(int64_t per_cu, int64_t groups) const {
-    return (unsigned)hpgq::accum::capped(std::min<int64_t>(per_cu * (int64_t)std::max(1, cus), groups), max_wg);
-  }
-
-  // a device buffer of at least `want` units in place of *p (cap: its size now), the old one retired
-  template <class T>
-  int grow(T **p, size_t unit, size_t want, bool zero) {
-    T *d = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&d), want * unit) != hipSuccess) return HPGQ_E_NOMEM;
-    if (zero) HPGQ_HIP_TRY(hipMemsetAsync(d, 0, want * unit, stream));
-    if (*p) retired.add(*p);
-    *p = d;
-    return HPGQ_OK;
-  }
-
-  int need_pos(int64_t n) {
-    if (n <= pos_cap) return HPGQ_OK;
-    const int64_t cap = std::max<int64_t>(n, pos_cap + pos_cap / 2);
-    const int rc = grow(&d_pos, 4, (size_t)cap, false);
-    if (rc == HPGQ_OK) pos_cap = cap;
-    return rc;
-  }
+  hpgq::cut::Ctx ctx() { return hpgq::cut::Ctx{stream, &retired, cus, max_wg}; }
 
   int settle() {
     HPGQ_HIP_TRY(hipSetDevice(device));
@@ -424,44 +302,17 @@ struct hpgq_clip {
 namespace {
 
 using namespace hpgq::clip;
-
-bool batch_ok(const hpgq_batch_t *b) { return b && b->num_reads >= 0 && (b->num_reads == 0 || (b->seq && b->data_indices)); }
+using hpgq::cut::batch_ok;
 
 // the find pass over b, async: positions to pos (never null), probes to probe (may be null)
 int find(hpgq_clip *q, const hpgq_batch_t *b, uint32_t *pos, uint8_t *probe) {
   return hpgq::accum::for_parts(b, nullptr, [&](const int32_t *ix, const uint8_t *, int64_t n) {
     const int64_t lo = ix - b->data_indices;
     // four workgroups of 512 threads per CU stay resident (8.6 KB of LDS each)
-    const dim3 grid(q->grid(4, (n + kGroup - 1) / kGroup));
+    const dim3 grid(q->ctx().grid(4, (n + kGroup - 1) / kGroup));
     auto *k = q->wide ? clip_find_kernel<true> : clip_find_kernel<false>;
     hipLaunchKernelGGL(k, grid, dim3(kWG), 0, q->stream, b->seq, ix, n, q->pr, pos + lo, probe ? probe + lo : nullptr,
                        q->d_scal);
-  });
-}
-
-// idx_out[0] = 0, idx_out[i + 1] = idx_out[i] + pos[i], then the copy; async
-int scan_and_copy(hpgq_clip *q, const hpgq_batch_t *b, const uint32_t *pos, char *seq_out, char *qual_out,
-                  int32_t *idx_out) {
-  HPGQ_HIP_TRY(hipMemsetAsync(idx_out, 0, 4, q->stream));
-  if (b->num_reads == 0) return HPGQ_OK;
-  const int first = (int)std::min<int64_t>(b->num_reads, hpgq::accum::kPart);
-  size_t tb = 0;
-  HPGQ_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, reinterpret_cast<const int32_t *>(pos), idx_out + 1, first,
-                                                q->stream));
-  if (tb > q->tmp_bytes) {
-    const int rc = q->grow(&q->d_tmp, 1, tb, false);
-    if (rc) return rc;
-    q->tmp_bytes = tb;
-  }
-  return hpgq::accum::for_parts(b, nullptr, [&](const int32_t *ix, const uint8_t *, int64_t n) {
-    const int64_t lo = ix - b->data_indices;
-    size_t bytes = q->tmp_bytes;
-    (void)hipcub::DeviceScan::InclusiveSum(q->d_tmp, bytes, reinterpret_cast<const int32_t *>(pos + lo), idx_out + lo + 1,
-                                           (int)n, q->stream);
-    if (lo) hipLaunchKernelGGL(clip_carry_kernel, dim3(1024), dim3(256), 0, q->stream, idx_out + lo + 1, n, idx_out + lo);
-    const dim3 grid(q->grid(4, (n + kGroup - 1) / kGroup));
-    hipLaunchKernelGGL(clip_copy_kernel, grid, dim3(kWG), 0, q->stream, b->seq, b->quality, ix, idx_out + lo, n, seq_out,
-                       qual_out);
   });
 }
 
@@ -513,11 +364,9 @@ void hpgq_clip_close(hpgq_clip_t *q) {
   if (q->stream) (void)hipStreamSynchronize(q->stream);
   q->retired.free_all();
   (void)hipFree(q->d_scal);
-  (void)hipFree(q->d_tmp);
-  (void)hipFree(q->d_pos);
-  (void)hipFree(q->o_seq);
-  (void)hipFree(q->o_qual);
-  (void)hipFree(q->o_idx);
+  q->scan.free();
+  q->pos.free();
+  q->kept.free();
   if (q->h_scal) (void)hipHostFree(q->h_scal);
   q->stream.close();
   delete q;
@@ -537,47 +386,23 @@ int hpgq_clip_device(hpgq_clip_t *q, const hpgq_batch_t *b, char *seq_out, char 
   if (b->num_reads && (!b->quality || !seq_out || !qual_out)) return HPGQ_E_INVALID;
   HPGQ_HIP_TRY(hipSetDevice(q->device));
   if (!pos_out && b->num_reads) {
-    const int rc = q->need_pos(b->num_reads);
+    const int rc = q->pos.need(q->ctx(), b->num_reads);
     if (rc) return rc;
-    pos_out = q->d_pos;
+    pos_out = q->pos.d;
   }
   const int rc = b->num_reads ? find(q, b, pos_out, probe_out) : HPGQ_OK;
-  return rc ? rc : scan_and_copy(q, b, pos_out, seq_out, qual_out, idx_out);
+  return rc ? rc : hpgq::cut::scan_and_copy(q->ctx(), q->scan, b, pos_out, seq_out, qual_out, idx_out);
 }
 
 int hpgq_clip_batch_device(hpgq_clip_t *q, const hpgq_batch_t *in, hpgq_batch_t *out) {
   if (!q || !batch_ok(in) || !out || (in->num_reads && !in->quality)) return HPGQ_E_INVALID;
   HPGQ_HIP_TRY(hipSetDevice(q->device));
   const hpgq_batch_t b = *in;   // (in and out may be the same struct)
-  // the input's bytes: its first and last offset live on the device
-  size_t bytes = 0;
-  if (b.num_reads) {
-    int32_t *ends = reinterpret_cast<int32_t *>(q->h_scal + kScalars);
-    HPGQ_HIP_TRY(hipMemcpyAsync(ends, b.data_indices, 4, hipMemcpyDeviceToHost, q->stream));
-    HPGQ_HIP_TRY(hipMemcpyAsync(ends + 1, b.data_indices + b.num_reads, 4, hipMemcpyDeviceToHost, q->stream));
-    HPGQ_HIP_TRY(hipStreamSynchronize(q->stream));
-    if (ends[1] < ends[0]) return HPGQ_E_INVALID;
-    bytes = (size_t)(ends[1] - ends[0]);
-  }
-  if (!q->o_seq || bytes > q->o_bytes) {
-    const size_t cap = std::max(bytes, q->o_bytes + q->o_bytes / 2);
-    int rc = q->grow(&q->o_seq, 1, cap + HPGQ_DEVICE_SLACK, true);
-    if (rc == HPGQ_OK) rc = q->grow(&q->o_qual, 1, cap + HPGQ_DEVICE_SLACK, true);
-    if (rc) return rc;
-    q->o_bytes = cap;
-  }
-  if (b.num_reads > q->o_reads) {
-    const int64_t cap = std::max<int64_t>(b.num_reads, q->o_reads + q->o_reads / 2);
-    const int rc = q->grow(&q->o_idx, 4, (size_t)cap + 1, false);
-    if (rc) return rc;
-    q->o_reads = cap;
-  }
-  const int rc = hpgq_clip_device(q, &b, q->o_seq, q->o_qual, q->o_idx, nullptr, nullptr);
+  int rc = q->kept.reserve(q->ctx(), b, reinterpret_cast<int32_t *>(q->h_scal + kScalars));
   if (rc) return rc;
-  out->num_reads = b.num_reads;
-  out->seq = q->o_seq;
-  out->quality = q->o_qual;
-  out->data_indices = q->o_idx;
+  rc = hpgq_clip_device(q, &b, q->kept.o_seq, q->kept.o_qual, q->kept.o_idx, nullptr, nullptr);
+  if (rc) return rc;
+  q->kept.give(out, b.num_reads);
   return HPGQ_OK;
 }
 

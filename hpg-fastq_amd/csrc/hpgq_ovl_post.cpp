@@ -1,0 +1,46 @@
+// hpgq_ovl_post.cpp — host side of `edit --clip-overlap`: the
+// overlap rule on one pair.  HIP-free, no device.
+//
+// For a candidate insert length F, s1[k] faces s2[F - 1 - k] for k in
+// [max(0, F - n2), min(n1, F)).  F is admissible iff that range holds at least
+// min_overlap positions and at most max_mismatches of them are not an A C G T
+// facing its complement.  The result is the greatest admissible F, 0 if none,
+// -1 for a pair with a mate longer than HPGQ_OVL_MAX_LEN.
+#include <cstdint>
+
+#include "../../include/hpgq.h"
+
+namespace {
+
+// the byte that faces b in a match, 0 if b is no base (no byte matches 0: 0 is no base)
+inline unsigned char comp(unsigned char b) {
+  switch (b) {
+    case 'A': return 'T';
+    case 'C': return 'G';
+    case 'G': return 'C';
+    case 'T': return 'A';
+    default: return 0;
+  }
+}
+
+}  // namespace
+
+extern "C" int64_t hpgq_ovl_find(const void *s1, size_t n1, const void *s2, size_t n2, int min_overlap, int max_mismatches) {
+  if (min_overlap < 8 || min_overlap > HPGQ_OVL_MAX_LEN || max_mismatches < 0 || max_mismatches > 255 ||
+      max_mismatches >= min_overlap || (!s1 && n1) || (!s2 && n2))
+    return -2;
+  if (n1 > HPGQ_OVL_MAX_LEN || n2 > HPGQ_OVL_MAX_LEN) return -1;
+  const unsigned char *a = static_cast<const unsigned char *>(s1), *b = static_cast<const unsigned char *>(s2);
+  const int64_t N1 = (int64_t)n1, N2 = (int64_t)n2;
+  for (int64_t F = N1 + N2 - min_overlap; F >= min_overlap; --F) {
+    const int64_t lo = F > N2 ? F - N2 : 0, hi = N1 < F ? N1 : F;
+    if (hi - lo < min_overlap) continue;
+    int mism = 0;
+    for (int64_t k = lo; k < hi && mism <= max_mismatches; ++k) {
+      const unsigned char c = comp(a[k]);
+      mism += !(c && b[F - 1 - k] == c);
+    }
+    if (mism <= max_mismatches) return F;
+  }
+  return 0;
+}

@@ -76,5 +76,24 @@ __device__ __forceinline__ v2u lane_load8(const __amdgpu_buffer_rsrc_t bytes, ui
   return __builtin_amdgcn_raw_buffer_load_b64(bytes, need ? (st & ~3u) + 4u * (uint32_t)lane : kNone, 0, 0);
 }
 
+// The lane's four bytes v (those past the read's end zeroed) as four 2-bit
+// codes c (base j at bits 2j .. 2j + 1) and four validity bits ok (base j at bit
+// j): the byte is exactly the one base with its code.
+__device__ __forceinline__ void pack4(uint32_t v, uint32_t &c, uint32_t &ok) {
+  const uint32_t x = v >> 1 & 0x03030303u;
+  const uint32_t isT = x >> 1 & ~x & 0x01010101u;
+  const uint32_t d = v ^ (0x41414141u + 2u * x + 15u * isT);
+  const uint32_t z = ~(((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
+  c = (x | x >> 6 | x >> 12 | x >> 18) & 0xFFu;
+  ok = (z >> 7 | z >> 14 | z >> 21 | z >> 28) & 0xFu;
+}
+
+// the lane's bytes st + 4 lane .. + 3 of a read with rem bytes from st on
+__device__ __forceinline__ uint32_t lane_bytes(v2u w, uint32_t st, int rem, int lane) {
+  const int nb = rem - 4 * lane;
+  const uint32_t raw = __builtin_amdgcn_alignbyte(w[1], w[0], st & 3u);
+  return nb >= 4 ? raw : nb <= 0 ? 0u : raw & ((1u << (8 * nb)) - 1u);
+}
+
 }  // namespace reads
 }  // namespace hpgq

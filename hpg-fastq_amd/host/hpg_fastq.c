@@ -153,6 +153,8 @@ int main(int argc, char **argv) {
     for (int a = 0; a < o->adapter_n; ++a) names[a] = o->adapter_names[a];
     if (cli_report_clip(o, o->adapter_n, names, &r.clip[m], p.paired ? mate_name[m] : cli_base_name(o->in_filename))) rc = 1;
   }
+  /* --clip-overlap: one file for the pairs, named as mate 1's report set would be */
+  if (r.ovl_on && cli_report_ovl(o, &r.ovl, mate_name[0])) rc = 1;
 
   if (!o->quiet) {
     printf("\n\nRESULTS\n");
@@ -171,6 +173,7 @@ int main(int argc, char **argv) {
     } else if (p.paired) {
       const char *ok = cmd == CMD_FILTER ? "passed" : "edit";
       if (cmd == CMD_EDIT) printf("Num. edited reads : %lu (mate 1)\n", (unsigned long)r.num_edited);
+      if (r.ovl_on) printf("Num. overlap-clipped pairs : %lu\n", (unsigned long)r.ovl.clipped);
       if (r.clip_on) printf("Num. clipped reads : %lu (mate 1)\n", (unsigned long)r.clip[0].clipped);
       printf("Num. passed pairs : %lu (%s/%s_1.fq, %s/%s_2.fq)\n", (unsigned long)r.num_passed, o->out_dirname, ok,
              o->out_dirname, ok);

@@ -48,6 +48,9 @@ typedef struct {
   char adapter_probes[HPGQ_ADAPT_MAX_PROBES][HPGQ_ADAPT_MAX_LEN + 1];
   int clip_on;              /* edit --clip-adapters: the set above, from --clip-adapter-file or the default */
   int clip_min_overlap;     /* --clip-min-overlap: 1 .. HPGQ_ADAPT_MAX_LEN */
+  int ovl_on;               /* edit --clip-overlap: paired input only */
+  int ovl_min_overlap;      /* --clip-overlap-min: 8 .. HPGQ_OVL_MAX_LEN */
+  int ovl_max_mismatches;   /* --clip-overlap-mismatches: 0 .. 255, below the minimum overlap */
   /* chaos game (old/main_hpg_fastq_old.c:185-189: --cg | --chaos-game, --k, --gs-filename) */
   int cg_on, k_cg;
   char *gs_filename;
@@ -118,6 +121,8 @@ typedef struct {
   uint64_t adapt_reads[2], adapt_with_any[2];
   int clip_on;              /* --clip-adapters: clip[] hold the mates' scalars, the workers' added */
   hpgq_clip_info_t clip[2];
+  int ovl_on;               /* --clip-overlap: ovl holds the pairs' scalars, the workers' added */
+  hpgq_ovl_info_t ovl;
   uint32_t *cg_seq, *cg_q;  /* --cg: table_seq / table_q [dim*dim] (malloc'd) */
   uint32_t cg_words;        /* fq_word_count */
   int cg_exact_calls;       /* chaos-game calls the exact simulation redid */
@@ -156,6 +161,8 @@ int cli_report_adapt(const cli_options_t *o, int nprobes, const char *const *nam
 /* --clip-adapters: <base>.adapter.clip.data from one mate's scalars */
 int cli_report_clip(const cli_options_t *o, int nprobes, const char *const *names, const hpgq_clip_info_t *info,
                     const char *base);
+/* --clip-overlap: <base>.overlap.clip.data from the pairs' scalars (base: mate 1's report base) */
+int cli_report_ovl(const cli_options_t *o, const hpgq_ovl_info_t *info, const char *base);
 const char *cli_base_name(const char *path);
 /* the report base names of the two mates: each input's base name, or
  * <base>_1 / <base>_2 for --interleaved (out: 2 x 4096 bytes) */

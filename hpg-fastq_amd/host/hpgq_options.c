@@ -10,7 +10,8 @@
  * --quality-dist-out, --overrepresented and its value flags
  *  and --duplication / --duplication-out
  * (§2.9), --adapters / --adapter-file / --adapters-out (§2.11), --clip-adapters /
- * --clip-adapter-file / --clip-min-overlap (§2.12).
+ * --clip-adapter-file / --clip-min-overlap (§2.12), --clip-overlap /
+ * --clip-overlap-min / --clip-overlap-mismatches (§2.13).
  * --quality-encoding is accepted by every command
  * (quirk Q11).
  */
@@ -101,6 +102,9 @@ static void usage(const cli_options_t *o) {
     printf("  --clip-adapters                 Cut every read at its first adapter, before the trim and the filter\n");
     printf("  --clip-adapter-file=<file>      Probes instead of the default set: lines of name, tab(s), sequence\n");
     printf("  --clip-min-overlap=<int>        Bases of an adapter a read must end in to be cut there (1-32, default 8)\n");
+    printf("  --clip-overlap                  Paired input: cut both mates where the sequenced fragment ends, found from the mates' overlap\n");
+    printf("  --clip-overlap-min=<int>        Bases the mates must overlap by (8-%d, default 30)\n", HPGQ_OVL_MAX_LEN);
+    printf("  --clip-overlap-mismatches=<int> Overlap positions that may differ (0-255, below the minimum overlap; default 5)\n");
   }
   printf("  --read-length-range=<string>    Read length range, eg. 80,110\n");
   printf("  --read-quality-range=<string>   Read quality range, eg. 20,40\n");
@@ -163,7 +167,7 @@ enum {
   O_RQRANGE, O_MAXN, O_MAXOOQ, O_GPU, O_LMAX, O_CHUNK, O_PRINT, O_COUNTERS, O_QUIET,
   O_KMERSOUT, O_CG, O_KCG, O_GS, O_GPUS, O_CGBATCH, O_CGOUT, O_GPUW, O_STREAMW, O_WHOOK, O_COPYT, O_PFT,
   O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT, O_DUP, O_DUPOUT, O_OVER, O_OVERMIN, O_OVERTOP, O_OVERBYTES,
-  O_ADAPT, O_ADAPTFILE, O_ADAPTOUT, O_CLIP, O_CLIPFILE, O_CLIPOV
+  O_ADAPT, O_ADAPTFILE, O_ADAPTOUT, O_CLIP, O_CLIPFILE, O_CLIPOV, O_OVL, O_OVLMIN, O_OVLMM
 };
 
 /* a whole-string decimal in [lo, hi] (u64), else the usage error */
@@ -204,6 +208,9 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   int adapter_values = 0;   /* --adapter-file or --adapters-out was given */
   int clip_values = 0;      /* --clip-adapter-file or --clip-min-overlap was given */
   o->clip_min_overlap = HPGQ_ADAPT_MIN_LEN;
+  int ovl_values = 0;       /* --clip-overlap-min or --clip-overlap-mismatches was given */
+  o->ovl_min_overlap = 30;
+  o->ovl_max_mismatches = 5;
   static const struct option longopts[] = {
       {"help", no_argument, 0, 'h'},
       {"fastq-file", required_argument, 0, 'f'},
@@ -253,6 +260,9 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
       {"clip-adapters", no_argument, 0, O_CLIP},
       {"clip-adapter-file", required_argument, 0, O_CLIPFILE},
       {"clip-min-overlap", required_argument, 0, O_CLIPOV},
+      {"clip-overlap", no_argument, 0, O_OVL},
+      {"clip-overlap-min", required_argument, 0, O_OVLMIN},
+      {"clip-overlap-mismatches", required_argument, 0, O_OVLMM},
       {"quiet", no_argument, 0, O_QUIET},
       {"stream-writer", no_argument, 0, O_STREAMW},
       {"writer-test-hook", required_argument, 0, O_WHOOK},
@@ -343,6 +353,18 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
         }
         if (c == O_CLIPOV) o->clip_min_overlap = count_arg(o, "clip-min-overlap", optarg, 1, HPGQ_ADAPT_MAX_LEN);
         break;
+      case O_OVL:
+      case O_OVLMIN:
+      case O_OVLMM:
+        if (command != CMD_EDIT) {   /* one line, before anything is opened or written */
+          fprintf(stderr, "hpg-fastq: --clip-overlap is an option of the edit command, not of %s\n", o->command_name);
+          exit(1);
+        }
+        if (c == O_OVL) o->ovl_on = 1;
+        else ovl_values = 1;
+        if (c == O_OVLMIN) o->ovl_min_overlap = count_arg(o, "clip-overlap-min", optarg, 8, HPGQ_OVL_MAX_LEN);
+        if (c == O_OVLMM) o->ovl_max_mismatches = count_arg(o, "clip-overlap-mismatches", optarg, 0, 255);
+        break;
       case O_CG:
         if (command != CMD_STATS) usage(o);
         o->cg_on = 1;
@@ -406,8 +428,21 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
     printf("\nError: --clip-adapter-file and --clip-min-overlap need --clip-adapters\n");
     usage(o);
   }
+  if (ovl_values && !o->ovl_on) {
+    printf("\nError: --clip-overlap-min and --clip-overlap-mismatches need --clip-overlap\n");
+    usage(o);
+  }
+  if (o->ovl_on && o->ovl_max_mismatches >= o->ovl_min_overlap) {
+    printf("\nError: --clip-overlap-mismatches (%d) must be below --clip-overlap-min (%d)\n", o->ovl_max_mismatches,
+           o->ovl_min_overlap);
+    usage(o);
+  }
   if (fq1) o->in_filename = fq1;
   o->paired = o->in_filename2 != NULL || o->interleaved;
+  if (o->ovl_on && !o->paired) {
+    printf("\nError: --clip-overlap needs paired-end input (--fq1/--fq2 or --interleaved)\n");
+    usage(o);
+  }
   if (o->paired && (o->kmers_on || o->cg_on)) {
     printf("\nError: --kmers and --cg are not available for paired-end input\n");
     usage(o);
@@ -526,6 +561,9 @@ void cli_display(const cli_options_t *o) {
            (unsigned long)o->overrep_min_count);
   if (o->adapters_on)
     printf("\tAdapter content      : %d probes, first occurrence per read (--adapters)\n", o->adapter_n);
+  if (o->ovl_on)
+    printf("\tOverlap clipping     : min overlap %d, max mismatches %d (--clip-overlap)\n", o->ovl_min_overlap,
+           o->ovl_max_mismatches);
   if (o->clip_on)
     printf("\tAdapter clipping     : %d probes, min overlap %d (--clip-adapters)\n", o->adapter_n, o->clip_min_overlap);
   printf("\n%s options\n", o->command == CMD_EDIT ? "Edit and filter" : "Filter");

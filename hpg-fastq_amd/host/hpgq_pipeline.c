@@ -814,6 +814,7 @@ typedef struct {
   hpgq_dup_t *dp[2];      /* --duplication: one hash table per mate, on the ctx stream */
   hpgq_adapt_t *ad[2];    /* --adapters: one table per mate, on the ctx stream */
   hpgq_clip_t *cl[2];     /* --clip-adapters: one handle per mate, on the ctx stream */
+  hpgq_ovl_t *ov;         /* --clip-overlap: one handle for the pair, on the ctx stream */
   hpgq_cgr_t *cg;
   uint8_t *d_mask;
   uint32_t *d_trim;
@@ -842,6 +843,9 @@ static int worker_open(worker_t *W) {
     for (int a = 0; a < o->adapter_n; ++a) probes[a] = o->adapter_probes[a];
     rc = hpgq_adapt_open(&W->ad[m], W->device, probes, o->adapter_n, W->p->lmax, hpgq_stream(W->ctx));
   }
+  /* --clip-overlap cuts both mates of a pair before anything else sees them */
+  if (rc == 0 && o->ovl_on)
+    rc = hpgq_ovl_open(&W->ov, W->device, o->ovl_min_overlap, o->ovl_max_mismatches, hpgq_stream(W->ctx));
   /* --clip-adapters cuts each mate on its own before the engine sees it */
   for (int m = 0; m < W->P->nmates && rc == 0 && o->clip_on; ++m) {
     const char *probes[HPGQ_ADAPT_MAX_PROBES];
@@ -877,6 +881,7 @@ static void worker_close(worker_t *W) {
   hpgq_adapt_close(W->ad[1]);
   hpgq_clip_close(W->cl[0]);
   hpgq_clip_close(W->cl[1]);
+  hpgq_ovl_close(W->ov);
   hpgq_dup_close(W->dp[0]);
   hpgq_dup_close(W->dp[1]);
   hpgq_cgr_close(W->cg);
@@ -968,6 +973,9 @@ static int worker_chunk(worker_t *W, slot_t *s) {
     }
   }
   if (rc || b[0].num_reads == 0) return rc;
+  /* --clip-overlap: from here on the pair is the kept reads, in buffers the
+   * handle owns until its next chunk; the probes below see what it kept */
+  if (W->ov && (rc = hpgq_ovl_batch_device(W->ov, &b[0], &b[1], &b[0], &b[1])) != 0) return rc;
   /* --clip-adapters: from here on the batch is the kept reads, in buffers the
    * handle owns until its next chunk (this chunk's hpgq_sync comes before that) */
   for (int m = 0; m < nm && W->cl[m]; ++m)
@@ -1292,6 +1300,21 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
       res->clip[m].nprobes = info.nprobes;
       res->clip[m].min_overlap = info.min_overlap;
     }
+  }
+  /* --clip-overlap: the workers' scalars added */
+  for (int w = 0; w < G && rc == 0 && o->ovl_on; ++w) {
+    hpgq_ovl_info_t info;
+    res->ovl_on = 1;
+    rc = hpgq_ovl_read(W[w].ov, &info);
+    if (rc) break;
+    res->ovl.pairs += info.pairs;
+    res->ovl.skipped += info.skipped;
+    res->ovl.overlapping += info.overlapping;
+    res->ovl.clipped += info.clipped;
+    res->ovl.bases_removed[0] += info.bases_removed[0];
+    res->ovl.bases_removed[1] += info.bases_removed[1];
+    res->ovl.min_overlap = info.min_overlap;
+    res->ovl.max_mismatches = info.max_mismatches;
   }
   /* --adapters: per mate, the workers' tables added at the longest worker's
    * positions (hpgq_adapt_add), and the two scalars added */

@@ -34,6 +34,7 @@ E_INVALID, E_NOMEM, E_STATE = -1, -3, -7
 QDIST_VALUES = 256
 DUP_LEVELS = 16
 ADAPT_MAX_PROBES, ADAPT_MIN_LEN, ADAPT_MAX_LEN = 32, 8, 32
+OVL_MAX_LEN = 512
 
 
 class HpgqError(RuntimeError):
@@ -103,6 +104,11 @@ class AdaptInfo(C.Structure):
 class ClipInfo(C.Structure):
     _fields_ = [("reads", C.c_uint64), ("clipped", C.c_uint64), ("bases_removed", C.c_uint64),
                 ("by_probe", C.c_uint64 * ADAPT_MAX_PROBES), ("nprobes", C.c_int32), ("min_overlap", C.c_int32)]
+
+
+class OvlInfo(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("skipped", C.c_uint64), ("overlapping", C.c_uint64), ("clipped", C.c_uint64),
+                ("bases_removed", C.c_uint64 * 2), ("min_overlap", C.c_int32), ("max_mismatches", C.c_int32)]
 
 
 class GsInfo(C.Structure):
@@ -251,6 +257,15 @@ _SIGS = [
     ("hpgq_clip_read", C.c_int, [C.c_void_p, C.POINTER(ClipInfo)]),
     ("hpgq_clip_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
     ("hpgq_clip_find", C.c_int64, [C.c_char_p, C.c_size_t, C.POINTER(C.c_char_p), C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    ("hpgq_ovl_open", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    ("hpgq_ovl_close", None, [C.c_void_p]),
+    ("hpgq_ovl_find_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("hpgq_ovl_batch_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Batch), C.POINTER(Batch), C.POINTER(Batch)]),
+    ("hpgq_ovl_sync", C.c_int, [C.c_void_p]),
+    ("hpgq_ovl_reset", C.c_int, [C.c_void_p]),
+    ("hpgq_ovl_read", C.c_int, [C.c_void_p, C.POINTER(OvlInfo)]),
+    ("hpgq_ovl_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
+    ("hpgq_ovl_find", C.c_int64, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int, C.c_int]),
     ("hpgq_synth_length", C.c_int32, [C.POINTER(Synth), C.c_int64]),
     ("hpgq_synth_indices_host", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p]),
     ("hpgq_synth_device", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p,

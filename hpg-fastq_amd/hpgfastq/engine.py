@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, AdaptInfo, ClipInfo, counters_len,
+from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, AdaptInfo, ClipInfo, OvlInfo, counters_len,
                    CGR_ALL_READS, ROUTES, E_PAIRING, QDIST_VALUES, DUP_LEVELS, HpgqError)
 
 # Kernel route for new Engines (tests / A/B: a key of ROUTES, or None for the
@@ -512,6 +512,48 @@ def clip_find(s, probes=None, min_overlap=8):
     if c == -2:
         raise HpgqError(-1, "hpgq_clip_find")
     return int(c), int(who.value)
+
+
+class OverlapClip(_Handle):
+    """hpgq_ovl: `edit --clip-overlap`, a pair's insert length from the overlap of
+    mate 1 with the reverse complement of mate 2 (at least `min_overlap` facing
+    bases, at most `max_mismatches` of them not complementary), both mates cut
+    there.  All pointers are device pointers (ints)."""
+
+    _prefix = "hpgq_ovl"
+
+    def __init__(self, min_overlap=30, max_mismatches=5, device=0, stream=None):
+        self.min_overlap, self.max_mismatches = int(min_overlap), int(max_mismatches)
+        self._open(device, self.min_overlap, self.max_mismatches, stream)
+
+    def find(self, mate1, mate2, insert_ptr=None, pos1_ptr=None, pos2_ptr=None):
+        """hpgq_ovl_find_device: insert int32 [n], pos1 / pos2 u32 [n], each unless None (async)."""
+        self._call("find_device", C.byref(mate1), C.byref(mate2), insert_ptr, pos1_ptr, pos2_ptr)
+
+    def clip_batch(self, mate1, mate2):
+        """hpgq_ovl_batch_device: both mates' kept reads as two Batches over buffers
+        the handle owns, valid until the next clip_batch or close."""
+        out1, out2 = Batch(), Batch()
+        self._call("batch_device", C.byref(mate1), C.byref(mate2), C.byref(out1), C.byref(out2))
+        return out1, out2
+
+    def info(self):
+        """dict(pairs, skipped, overlapping, clipped, bases_removed [2], min_overlap, max_mismatches); synchronises."""
+        i = OvlInfo()
+        self._call("read", C.byref(i))
+        return dict(pairs=int(i.pairs), skipped=int(i.skipped), overlapping=int(i.overlapping), clipped=int(i.clipped),
+                    bases_removed=[int(x) for x in i.bases_removed], min_overlap=int(i.min_overlap),
+                    max_mismatches=int(i.max_mismatches))
+
+
+def ovl_find(s1, s2, min_overlap=30, max_mismatches=5):
+    """hpgq_ovl_find: F*, 0 or -1 (skipped) of the pair of byte strings
+    (HpgqError -1 for parameters that break the rules)."""
+    s1, s2 = bytes(s1), bytes(s2)
+    f = lib.hpgq_ovl_find(s1, len(s1), s2, len(s2), int(min_overlap), int(max_mismatches))
+    if f == -2:
+        raise HpgqError(-1, "hpgq_ovl_find")
+    return int(f)
 
 
 def _levels_dict(lv):

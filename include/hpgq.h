@@ -833,6 +833,63 @@ int64_t hpgq_clip_find(const void *s, size_t n, const char *const *probes, int n
                        int min_overlap, int *probe);
 
 /* ---------------------------------------------------------------------- */
+/* edit --clip-overlap: cut paired reads at the insert end                  */
+/* ---------------------------------------------------------------------- */
+
+/*
+ * Build-defined.  A pair is mate 1 s1[0, n1) and mate 2
+ * s2[0, n2); comp maps A<->T and C<->G, upper case only.  min_overlap is
+ * 8 .. HPGQ_OVL_MAX_LEN, max_mismatches M is 0 .. 255 and below min_overlap.
+ * A pair with a mate longer than HPGQ_OVL_MAX_LEN is skipped: result -1,
+ * nothing cut.  For a candidate insert length F, lo = max(0, F - n2),
+ * hi = min(n1, F), ov(F) = hi - lo, and for k in [lo, hi) byte s1[k] faces
+ * s2[F - 1 - k]; mism(F) counts the k for which it is not true that both bytes
+ * are one of A C G T and s2[F - 1 - k] == comp(s1[k]) (N, lower case and every
+ * other byte value mismatch, also against themselves).  F is admissible iff
+ * ov(F) >= min_overlap and mism(F) <= M; F* is the greatest admissible F, 0 if
+ * there is none.  With F* > 0 mate 1 keeps min(n1, F*) bytes of sequence and
+ * quality and mate 2 min(n2, F*); otherwise both keep everything.  Nothing
+ * behind a read's last byte counts.  The scalars are plain u64 sums over every
+ * batch since open or reset.
+ *
+ * Input as hpgq_clip_device, two batches of the same num_reads.  The inputs
+ * are never written.  Everything runs on the handle's stream.
+ */
+#define HPGQ_OVL_MAX_LEN 512
+typedef struct hpgq_ovl hpgq_ovl_t;
+typedef struct hpgq_ovl_info {
+  uint64_t pairs, skipped, overlapping, clipped, bases_removed[2];
+  int32_t min_overlap, max_mismatches;
+} hpgq_ovl_info_t;
+
+/* stream: as hpgq_kmers_open.  HPGQ_E_INVALID before any device call. */
+int  hpgq_ovl_open(hpgq_ovl_t **ov, int device, int min_overlap, int max_mismatches, void *stream);
+void hpgq_ovl_close(hpgq_ovl_t *ov);
+/* results only (async): insert_out[i] = F*, 0 or -1 (int32), pos1_out[i] /
+ * pos2_out[i] = the bytes mate 1 / mate 2 keeps (uint32); device pointers of
+ * num_reads elements, each may be NULL */
+int  hpgq_ovl_find_device(hpgq_ovl_t *ov, const hpgq_batch_t *m1, const hpgq_batch_t *m2,
+                          int32_t *insert_out, uint32_t *pos1_out, uint32_t *pos2_out);
+/* find, then both mates' kept reads back to back into buffers the handle owns
+ * (the contract of hpgq_clip_batch_device: valid until the next call on this
+ * handle or its close; out1 / out2 may be m1 / m2; waits for the stream for
+ * the inputs' sizes, the cut itself is async) */
+int  hpgq_ovl_batch_device(hpgq_ovl_t *ov, const hpgq_batch_t *m1, const hpgq_batch_t *m2,
+                           hpgq_batch_t *out1, hpgq_batch_t *out2);
+int  hpgq_ovl_sync(hpgq_ovl_t *ov);
+/* zero the scalars (async); the parameters stay */
+int  hpgq_ovl_reset(hpgq_ovl_t *ov);
+/* the scalars since open or reset.  Synchronises. */
+int  hpgq_ovl_read(hpgq_ovl_t *ov, hpgq_ovl_info_t *info);
+/* Tests only: at most max_wg workgroups per kernel (0, the default: no limit). */
+int  hpgq_ovl_debug_set_max_workgroups(hpgq_ovl_t *ov, int max_wg);
+/* Host only, no device (csrc/hpgq_ovl_post.cpp): the rule above on one pair.
+ * Returns F*, 0, -1 (skipped) or -2 (parameters that break the rules, or a
+ * NULL mate with bytes). */
+int64_t hpgq_ovl_find(const void *s1, size_t n1, const void *s2, size_t n2, int min_overlap,
+                      int max_mismatches);
+
+/* ---------------------------------------------------------------------- */
 /* FASTQ text -> device batch (the parsing half of the producer's          */
 /* fastq_fread_se, src/stats_fastq.c:183, moved onto the GPU)              */
 /* ---------------------------------------------------------------------- */

@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""Rate of hpgq_ovl_find_device and hpgq_ovl_batch_device next
+to hpgq_clip_find_device on both mates of the same device batches, in one
+session.
+
+Shapes: 10 M x 150 bp and 8.59 M x 250 bp pairs of one length.  Fillings: random
+A C G T mates that have nothing to do with each other ("none"); every pair from a
+fragment of L + 1 .. 2 L - 30 bases, so the mates overlap and nothing is cut
+("overlap"); 20 % of the pairs from a fragment of 30 .. L - 1 bases, both mates
+going on with random bases behind it ("readthrough").  Every call is timed
+between two HIP events on the stream it runs on, after --warmup calls.  Prints
+one JSON line per shape and filling: us per call (median, min, max) of the
+overlap find, of find + scan + copy of both mates, and of the two adapter find
+passes (default probes, min overlap 8) together; ovl_vs_two_finds is the ratio of
+the medians.  Everything also goes to --out (default profiles/ovl_rate.json).  Not a
+test; fails without a GPU.
+
+    python tools/ovl_rate.py [--pairs 10000000] [--steps 20] [--warmup 5] [--out profiles/ovl_rate.json]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "hpg-fastq_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from adapt_rate import timed, summary   # noqa: E402
+
+
+def fill_pairs(torch, seq1, seq2, n, L, filling, gen):
+    """The n x L bases of both mates for one filling -> the pairs made from a fragment."""
+    lut = torch.tensor(list(b"ACGT"), dtype=torch.uint8, device="cuda")
+    comp = torch.tensor([3, 2, 1, 0], dtype=torch.int64, device="cuda")          # index of the complement in ACGT
+    v1, v2 = seq1[:n * L].view(n, L), seq2[:n * L].view(n, L)
+    made = 0
+    step = 1 << 20
+    col = torch.arange(L, device="cuda")[None, :]
+    for lo in range(0, n, step):
+        m = min(step, n - lo)
+        frag = torch.randint(0, 4, (m, 2 * L), dtype=torch.int64, device="cuda", generator=gen)
+        other = torch.randint(0, 4, (m, L), dtype=torch.int64, device="cuda", generator=gen)
+        a, b = frag[:, :L], other
+        if filling != "none":
+            if filling == "overlap":
+                F = torch.randint(L + 1, 2 * L - 30 + 1, (m, 1), device="cuda", generator=gen)
+                on = torch.ones((m, 1), dtype=torch.bool, device="cuda")
+            else:
+                F = torch.randint(30, L, (m, 1), device="cuda", generator=gen)
+                on = torch.rand((m, 1), device="cuda", generator=gen) < 0.2
+            # mate 2 base j is the complement of fragment base F - 1 - j; behind the fragment both mates are random
+            src = (F - 1 - col).clamp(0, 2 * L - 1)
+            rc = comp[frag.gather(1, src)]
+            b = torch.where(on & (col < F), rc, other)
+            a = torch.where(on & (col >= F), other.flip(1), a)
+            made += int(on.sum().item())
+        v1[lo:lo + m] = lut[a]
+        v2[lo:lo + m] = lut[b]
+    return made
+
+
+def write_profile(path, rows, steps, warmup):
+    what = (f"tools/ovl_rate.py --steps {steps} --warmup {warmup} on one MI355X, one session: hpgq_ovl_find_device (min overlap "
+            "30, max mismatches 5), hpgq_ovl_batch_device (find + scan + copy of both mates) and hpgq_clip_find_device on "
+            "both mates of the same device batches (default probes, min overlap 8, no winners' byte); HIP events on the "
+            "stream, us per call.  Fillings: none = unrelated random mates; overlap = every pair from a fragment of "
+            "L+1 .. 2L-30 bases (found, nothing cut); readthrough = 20 % of the pairs from a fragment of 30 .. L-1 bases, "
+            "random bases behind it in both mates.")
+    with open(path, "w") as f:
+        f.write(json.dumps({"what": what, "results": rows}, indent=1) + "\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=10_000_000)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ovl_rate.json"))
+    a = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("ovl_rate: no GPU (rates are measured on the device or not at all)")
+    import hpgfastq as H
+
+    props = torch.cuda.get_device_properties(0)
+    box = {"device": torch.cuda.get_device_name(0), "cus": props.multi_processor_count, "host": os.uname().nodename}
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(7)
+    stream = torch.cuda.Stream()
+    sp = stream.cuda_stream
+    calls = a.warmup + a.steps
+    rows = []
+    for name, L in (("150bp", 150), ("250bp", 250)):
+        n = min(a.pairs, (2 ** 31 - 1024) // L)   # data_indices are int32: < 2 GiB of bases per batch
+        total = n * L
+        idx = (torch.arange(n + 1, dtype=torch.int64, device="cuda") * L).to(torch.int32)
+        seq = [torch.zeros(total + H.DEVICE_SLACK, dtype=torch.uint8, device="cuda") for _ in range(2)]
+        qual = torch.full((total + H.DEVICE_SLACK,), ord("I"), dtype=torch.uint8, device="cuda")
+        ins = torch.empty(n, dtype=torch.int32, device="cuda")
+        pos = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(2)]
+        b = [H.engine.device_batch(n, s.data_ptr(), qual.data_ptr(), idx.data_ptr()) for s in seq]
+        for filling in ("none", "overlap", "readthrough"):
+            made = fill_pairs(torch, seq[0], seq[1], n, L, filling, gen)
+            torch.cuda.synchronize()
+            with H.AdapterClip(None, 8, stream=sp) as cl:
+                def two_finds():
+                    cl.find(b[0], pos[0].data_ptr(), None)
+                    cl.find(b[1], pos[1].data_ptr(), None)
+                clip_us = timed(torch, stream, two_finds, a.warmup, a.steps)
+                cl.sync()
+            with H.OverlapClip(30, 5, stream=sp) as ov:
+                find_us = timed(torch, stream, lambda: ov.find(b[0], b[1], ins.data_ptr(), pos[0].data_ptr(), pos[1].data_ptr()),
+                                a.warmup, a.steps)
+                info = ov.info()
+                ov.reset()
+                cut_us = timed(torch, stream, lambda: ov.clip_batch(b[0], b[1]), a.warmup, a.steps)
+                ov.sync()
+            per = {k: (v // calls if isinstance(v, int) else [x // calls for x in v]) for k, v in info.items()
+                   if k not in ("min_overlap", "max_mismatches")}
+            assert per["pairs"] == n and per["skipped"] == 0, info
+            if filling == "none":
+                assert per["overlapping"] < n // 1000, info
+            if filling == "overlap":
+                assert per["overlapping"] == n and per["clipped"] == 0, info
+            if filling == "readthrough":
+                assert per["clipped"] >= made, info
+            kept = total * 2 - sum(per["bases_removed"])
+            f, c = summary(find_us, 2 * total + 20 * n, n), summary(clip_us, 2 * total + 16 * n, n)
+            res = {"tool": "ovl_rate", "shape": name, "pairs": n, "read_length": L, "bases": 2 * total, "min_overlap": 30,
+                   "max_mismatches": 5, "filling": filling, "fragment_pairs": made, "per_call": per, "steps": a.steps,
+                   "warmup": a.warmup, **box,
+                   # find: both mates' bases and offsets in, 12 bytes per pair out
+                   "ovl_find": f,
+                   # find + two scans + two copies: the kept bytes of sequence and quality move once each way
+                   "ovl_batch": summary(cut_us, 2 * total + 24 * n + 4 * kept + 16 * n, n),
+                   "clip_find_both_mates": c,
+                   "ovl_vs_two_finds": round(f["us_median"] / c["us_median"], 3)}
+            print(json.dumps(res), flush=True)
+            rows.append(res)
+        del seq, qual, idx, ins, pos
+        torch.cuda.empty_cache()
+    write_profile(a.out, rows, a.steps, a.warmup)
+
+
+if __name__ == "__main__":
+    main()
