@@ -68,37 +68,29 @@ int for_parts(const hpgq_batch_t *b, const uint8_t *mask, Launch launch) {
   return HPGQ_OK;
 }
 
-// A counter per read position (hpgq_qdist, hpgq_adapt): a table of `rows` rows
-// of row_bytes of u64 on the device, position-major so that growing appends
-// rows; nscal u64 sums beside it; and two flags the kernel keeps, [the longest
-// counted read, the counted reads longer than the rows].
-struct Positions {
+// What every handle that runs per-read kernels on one stream owns (hpgq_qdist,
+// hpgq_adapt, and through hpgq_cut.h hpgq_clip and hpgq_ovl): the device, the
+// stream, the buffers it replaced, the grid limits, and nscal u64 sums the
+// kernels add to, with their pinned copy.
+struct Handle {
   int device = 0;
   Stream stream;
-  Retired retired;                          // tables replaced by a larger one
-  unsigned long long *d_table = nullptr;    // [rows][row_bytes / 8]
-  int64_t rows = 0;
-  size_t row_bytes = 0;
+  Retired retired;                          // owned buffers replaced by larger ones
   int nscal = 0;
   unsigned long long *d_scal = nullptr;     // [nscal]
-  uint32_t *d_flags = nullptr;
-  unsigned long long *h_scal = nullptr;     // pinned: the scalars, then the two flags
+  unsigned long long *h_scal = nullptr;     // pinned: the scalars, then one word that is the derived handle's (h_extra)
   int cus = 0, max_wg = 0;
 
-  const uint32_t *h_flags() const { return reinterpret_cast<const uint32_t *>(h_scal + nscal); }
+  void *h_extra() const { return h_scal + nscal; }
 
-  // After use_device.  Everything allocated and zeroed; on an error close() frees what there is.
-  int open(int dev, void *callers_stream, int64_t nrows, size_t nrow_bytes, int scalars) {
+  // After use_device.  The scalars allocated and zeroed; on an error close() frees what there is.
+  int open(int dev, void *callers_stream, int scalars) {
     device = dev;
-    rows = nrows;
-    row_bytes = nrow_bytes;
     nscal = scalars;
     const int rc = stream.open(callers_stream);
     if (rc) return rc;
-    const size_t hs = (size_t)nscal * 8 + 8;
-    if (hipMalloc(&d_table, (size_t)rows * row_bytes) != hipSuccess ||
-        (nscal && hipMalloc(&d_scal, (size_t)nscal * 8) != hipSuccess) || hipMalloc(&d_flags, 8) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void **>(&h_scal), hs, hipHostMallocDefault) != hipSuccess)
+    if ((nscal && hipMalloc(&d_scal, (size_t)nscal * 8) != hipSuccess) ||
+        hipHostMalloc(reinterpret_cast<void **>(&h_scal), (size_t)nscal * 8 + 8, hipHostMallocDefault) != hipSuccess)
       return HPGQ_E_NOMEM;
     for (int i = 0; i <= nscal; ++i) h_scal[i] = 0;
     if (zero() != hipSuccess ||
@@ -107,27 +99,83 @@ struct Positions {
     return HPGQ_OK;
   }
 
+  // Waits for the stream.  The derived handle frees its own buffers after it.
   void close() {
     (void)hipSetDevice(device);
     if (stream) (void)hipStreamSynchronize(stream);
     retired.free_all();
-    (void)hipFree(d_table);
     (void)hipFree(d_scal);
-    (void)hipFree(d_flags);
     if (h_scal) (void)hipHostFree(h_scal);
     stream.close();
   }
 
-  hipError_t zero() {
-    hipError_t e = hipMemsetAsync(d_table, 0, (size_t)rows * row_bytes, stream);
-    if (e == hipSuccess && nscal) e = hipMemsetAsync(d_scal, 0, (size_t)nscal * 8, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flags, 0, 8, stream);
-    return e;
-  }
+  hipError_t zero() { return nscal ? hipMemsetAsync(d_scal, 0, (size_t)nscal * 8, stream) : hipSuccess; }
 
   int reset() {
     HPGQ_HIP_TRY(hipSetDevice(device));
     HPGQ_HIP_TRY(zero());
+    return HPGQ_OK;
+  }
+
+  // fetch the scalars, wait for the stream, free the replaced buffers
+  int settle() {
+    HPGQ_HIP_TRY(hipSetDevice(device));
+    if (nscal) HPGQ_HIP_TRY(hipMemcpyAsync(h_scal, d_scal, (size_t)nscal * 8, hipMemcpyDeviceToHost, stream));
+    HPGQ_HIP_TRY(hipStreamSynchronize(stream));
+    retired.free_all();
+    return HPGQ_OK;
+  }
+
+  // persistent grid: per_cu workgroups per CU, no more than there are read groups
+  unsigned grid(int64_t per_cu, int64_t groups) const {
+    return (unsigned)capped(std::min<int64_t>(per_cu * (int64_t)std::max(1, cus), groups), max_wg);
+  }
+
+  int set_max_workgroups(int n) {
+    if (n < 0) return HPGQ_E_INVALID;
+    max_wg = n;
+    return HPGQ_OK;
+  }
+};
+
+// A counter per read position (hpgq_qdist, hpgq_adapt): a table of `rows` rows
+// of row_bytes of u64 on the device, position-major so that growing appends
+// rows; the handle's sums beside it; and two flags the kernel keeps, [the
+// longest counted read, the counted reads longer than the rows].
+struct Positions : Handle {
+  unsigned long long *d_table = nullptr;    // [rows][row_bytes / 8]
+  int64_t rows = 0;
+  size_t row_bytes = 0;
+  uint32_t *d_flags = nullptr;              // (their pinned copy: h_extra)
+
+  const uint32_t *h_flags() const { return static_cast<const uint32_t *>(h_extra()); }
+
+  // After use_device.  Everything allocated and zeroed; on an error close() frees what there is.
+  int open(int dev, void *callers_stream, int64_t nrows, size_t nrow_bytes, int scalars) {
+    rows = nrows;
+    row_bytes = nrow_bytes;
+    const int rc = Handle::open(dev, callers_stream, scalars);
+    if (rc) return rc;
+    if (hipMalloc(&d_table, (size_t)rows * row_bytes) != hipSuccess || hipMalloc(&d_flags, 8) != hipSuccess)
+      return HPGQ_E_NOMEM;
+    return zero_table() == hipSuccess ? HPGQ_OK : HPGQ_E_HIP;
+  }
+
+  void close() {
+    Handle::close();
+    (void)hipFree(d_table);
+    (void)hipFree(d_flags);
+  }
+
+  hipError_t zero_table() {
+    const hipError_t e = hipMemsetAsync(d_table, 0, (size_t)rows * row_bytes, stream);
+    return e == hipSuccess ? hipMemsetAsync(d_flags, 0, 8, stream) : e;
+  }
+
+  int reset() {
+    const int rc = Handle::reset();
+    if (rc) return rc;
+    HPGQ_HIP_TRY(zero_table());
     return HPGQ_OK;
   }
 
@@ -154,30 +202,18 @@ struct Positions {
     return HPGQ_OK;
   }
 
-  // wait for the stream, fetch the scalars and the flags, free the replaced tables
+  // the handle's, with the flags fetched before the wait
   int settle() {
     HPGQ_HIP_TRY(hipSetDevice(device));
-    if (nscal) HPGQ_HIP_TRY(hipMemcpyAsync(h_scal, d_scal, (size_t)nscal * 8, hipMemcpyDeviceToHost, stream));
-    HPGQ_HIP_TRY(hipMemcpyAsync(h_scal + nscal, d_flags, 8, hipMemcpyDeviceToHost, stream));
-    HPGQ_HIP_TRY(hipStreamSynchronize(stream));
-    retired.free_all();
+    HPGQ_HIP_TRY(hipMemcpyAsync(h_extra(), d_flags, 8, hipMemcpyDeviceToHost, stream));
+    const int rc = Handle::settle();
+    if (rc) return rc;
     return h_flags()[1] ? HPGQ_E_READ_TOO_LONG : HPGQ_OK;
   }
 
   // the first np rows to the host (after settle)
   int read_rows(void *host, size_t np) {
     if (np) HPGQ_HIP_TRY(hipMemcpy(host, d_table, np * row_bytes, hipMemcpyDeviceToHost));
-    return HPGQ_OK;
-  }
-
-  // persistent grid: per_cu workgroups per CU, no more than there are read groups
-  unsigned grid(int64_t per_cu, int64_t groups) const {
-    return (unsigned)capped(std::min<int64_t>(per_cu * (int64_t)std::max(1, cus), groups), max_wg);
-  }
-
-  int set_max_workgroups(int n) {
-    if (n < 0) return HPGQ_E_INVALID;
-    max_wg = n;
     return HPGQ_OK;
   }
 };

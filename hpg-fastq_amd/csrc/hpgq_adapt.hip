@@ -11,32 +11,15 @@
 // the whole read: the found-mask of a read (one bit per probe, wave-uniform)
 // lives across the steps of a long read.
 //
-// A step: lane l takes the read's bytes p0 + 4l .. p0 + 4l + 3 (one 8-byte
-// dword-aligned load, hpgq_reads.h, and v_alignbyte), zeroes those past
-// the read's end, and packs them, four bytes at once, into four 2-bit base
-// codes ((b >> 1) & 3: A 0, C 1, T 2, G 3) and four validity bits: the byte is
-// exactly the one base with its code.  2-bit codes alias (a, N and 250 other
-// values share them), so a window matches only if the codes are equal AND its
-// first K bases are all valid.  Bytes past the read's end -- the next read's
-// bases, the slack -- are invalid, so no window reaches over it.
-//
-// Windows cross lanes.  Each lane builds the codes and validity bits of the
-// bases of lanes l .. l + H by doubling with ds_bpermute (codes and validity
-// packed into one word while they fit): H = 3 and two permutes give 16 bases in
-// a 32-bit window for probes of up to 13 bases (NARROW: the default set); H = 8
-// and five permutes give 36 bases in a 64 + 8 bit window for probes of up to 32
-// (WIDE).  The last H lanes of a step only supply bases: a step covers the
-// starts p0 .. p0 + S - 1, S = 4 (64 - H) = 244 or 224, and the next step
-// starts at p0 + S, so no window needs the following step's bytes.  150 and
-// 250 bp reads with the default set take one step.
-//
-// Prefilter: every probe has at least 8 bases, so the workgroup keeps a 65,536
-// bit map of the set's 8-base prefixes (16 code bits) in LDS; a start is a
-// candidate iff its next 8 bases are valid and their bit is set: one ds_read
-// and a few VALU per start, and one ballot per step.  Almost every step of
-// real data ends there (DESIGN.md 4.13 has both variants' times: without the
-// bitmap the default set took 1.6 - 2 x as long on reads without adapters, 32
-// probes 2.7 - 5 x).
+// The step -- the lane's four bases as 2-bit codes and validity bits, the
+// windows across lanes (H = 3 lanes behind its own for NARROW, the default set;
+// H = 8 for WIDE, a probe of more than 13 bases), the workgroup's bitmap of the
+// set's 8-base prefixes that ends almost every step of real data after one
+// ballot -- is hpgq_probes.h's, shared with hpgq_clip.hip.  A step covers
+// S = 4 (64 - H) = 244 or 224 starts: 150 and 250 bp reads with the default set
+// take one.  (DESIGN.md 4.13 has the times with and without the bitmap:
+// without it the default set took 1.6 - 2 x as long on reads without adapters,
+// 32 probes 2.7 - 5 x.)
 //
 // A step with a candidate walks the probes: one masked compare per start
 // ((window & mask_a) == code_a, and the valid run from the start >= K_a, one
@@ -54,49 +37,33 @@
 // rows take one add per workgroup.  A counted read longer than the rows is not
 // scanned.
 #include "hpgq_accum.h"
+#include "hpgq_probes.h"
 #include "hpgq_reads.h"
 
 #include <algorithm>
-#include <climits>
-#include <cstring>
 #include <vector>
 
 namespace hpgq {
 namespace adapt {
 
 constexpr int kP = 256;     // positions whose counts stay on chip
-constexpr int kMaxProbes = HPGQ_ADAPT_MAX_PROBES;
 constexpr int kWG = 512;
 constexpr int kWaves = kWG / 64;
 constexpr int kR = 16;      // reads per wave step
 constexpr int kPre = 4;     // of them with their first load in flight
 constexpr int kGroup = kWaves * kR;   // reads per workgroup step
-constexpr int kNarrowMax = 13;        // longest probe of the 32-bit window: 16 bases less the 3 a start may skip
+using probes::kBitmapWords;
+using probes::kMaxProbes;
+using probes::Probes;
 using reads::v2u;
-constexpr int kBitmapWords = 65536 / 32;   // one bit per 8-base prefix (16 code bits)
-static_assert(kR % kPre == 0, "the reads of a wave step go in blocks of kPre");
-static_assert(kMaxProbes == 32, "the found-mask is one 32-bit word");
-
-// the probe set as the kernel takes it (by value: scalar loads)
-struct Probes {
-  uint64_t code[kMaxProbes];   // base j at bits 2j .. 2j + 1
-  uint32_t len[kMaxProbes];
-  int32_t n, kmin;
-};
-
-// the 2-bit code of an A C G T byte
-__host__ __device__ inline uint32_t code_of(uint32_t b) { return (b >> 1) & 3u; }
-
-__device__ __forceinline__ uint32_t pull(uint32_t v, int lane, int d) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + d) & 63) * 4, (int)v);
-}
 
 // One counted read of len <= rows bytes at st0 (from the descriptor's base);
-// w0: its first step's load.  Everything but the lane's bytes is wave-uniform.
+// w0: its first step's load; lp: lane a's probe a.  Everything but the lane's
+// bytes is wave-uniform.
 template <bool WIDE>
 __device__ __forceinline__ uint32_t scan_read(const __amdgpu_buffer_rsrc_t rq, const Probes &pr, int lane, uint32_t st0,
-                                              int len, v2u w0, uint32_t pc_lo, uint32_t pc_hi, uint32_t pk,
-                                              uint32_t *t, const uint32_t *bm, unsigned long long *first) {
+                                              int len, v2u w0, const probes::LaneProbe lp, uint32_t *t,
+                                              const uint32_t *bm, unsigned long long *first) {
   constexpr int H = WIDE ? 8 : 3;          // lanes after its own a lane's windows reach into
   constexpr int S = 4 * (64 - H);          // starts per step
   const uint32_t all = pr.n == kMaxProbes ? 0xFFFFFFFFu : (1u << pr.n) - 1u;
@@ -105,33 +72,16 @@ __device__ __forceinline__ uint32_t scan_read(const __amdgpu_buffer_rsrc_t rq, c
     const int rem = len - p0;
     const uint32_t st = st0 + (uint32_t)p0;
     const v2u w = p0 == 0 ? w0 : reads::lane_load8(rq, st, rem, lane);
-    // positions p0 + 4 lane + [0, 4); the bytes past the read's end become 0, which is no base
-    const int nb = rem - 4 * lane;
-    const uint32_t raw = __builtin_amdgcn_alignbyte(w[1], w[0], st & 3u);
-    const uint32_t v = nb >= 4 ? raw : nb <= 0 ? 0u : raw & ((1u << (8 * nb)) - 1u);
-    // the four bytes at once: x the code of each byte, `want` the one byte with
-    // that code that is a base (0x41 + 2 code, and T = 0x54 for code 2), z bit 7
-    // of every byte that equals it (the zero-byte test of v ^ want)
-    const uint32_t x = v >> 1 & 0x03030303u;
-    const uint32_t isT = x >> 1 & ~x & 0x01010101u;
-    const uint32_t d = v ^ (0x41414141u + 2u * x + 15u * isT);
-    const uint32_t z = ~(((d & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | d) & 0x80808080u;
-    const uint32_t c = (x | x >> 6 | x >> 12 | x >> 18) & 0xFFu;          // base j at bits 2j .. 2j + 1
-    const uint32_t ok = (z >> 7 | z >> 14 | z >> 21 | z >> 28) & 0xFu;    // base j at bit j
-    // 16 bases from lanes l .. l + 3: codes 32 bits, validity 16
-    const uint32_t x1 = c | ok << 8;
-    const uint32_t y1 = pull(x1, lane, 1);
-    const uint32_t c2 = c | (y1 & 0xFFu) << 8, ok2 = ok | (y1 >> 8 & 0xFu) << 4;
-    const uint32_t y2 = pull(c2 | ok2 << 16, lane, 2);
-    const uint32_t c4 = c2 | y2 << 16, ok4 = ok2 | (y2 >> 16 & 0xFFu) << 8;
+    // positions p0 + 4 lane + [0, 4): 16 bases from lanes l .. l + 3 (codes 32 bits, validity 16) and the prefilter
+    const probes::Window s = probes::window(w, st, rem, lane, bm);
     uint64_t win[4];    // the bases from start k on (WIDE: 32 of them, else 16 - k)
     uint32_t val[4];    // their validity bits (WIDE: 32, else 16 - k)
     if (WIDE) {
-      const uint64_t c8 = (uint64_t)c4 | (uint64_t)pull(c4, lane, 4) << 32;
-      const uint32_t ok8 = ok4 | pull(ok4, lane, 4) << 16;
-      const uint32_t y9 = pull(x1, lane, 8);
-      const uint64_t c9 = y9 & 0xFFu;
-      const uint32_t ok9 = y9 >> 8 & 0xFu;
+      const probes::Wide x = probes::pull_wide(s, lane);
+      const uint64_t c8 = (uint64_t)s.c4 | (uint64_t)x.c8_hi << 32;
+      const uint32_t ok8 = s.ok4 | x.ok8_hi << 16;
+      const uint64_t c9 = x.y9 & 0xFFu;
+      const uint32_t ok9 = x.y9 >> 8 & 0xFu;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         win[k] = k ? c8 >> (2 * k) | c9 << (64 - 2 * k) : c8;
@@ -140,34 +90,23 @@ __device__ __forceinline__ uint32_t scan_read(const __amdgpu_buffer_rsrc_t rq, c
     } else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        win[k] = c4 >> (2 * k);
-        val[k] = ok4 >> k;
+        win[k] = s.c4 >> (2 * k);
+        val[k] = s.ok4 >> k;
       }
     }
-    // Prefilter: every probe has at least 8 bases, so a probe can start only
-    // where the next 8 bases are valid (r8: ok4 folded three times) and their 16
-    // code bits are the first 8 bases of some probe (one bit of bm).  Most
-    // steps of real data end here.
     const bool starts = lane < 64 - H;   // the last H lanes only supply bases
-    const uint32_t r2 = ok4 & ok4 >> 1, r4 = r2 & r2 >> 2, r8 = r4 & r4 >> 4;
-    uint32_t cand = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t ix8 = (uint32_t)win[k] & 0xFFFFu;
-      cand |= (bm[ix8 >> 5] >> (ix8 & 31u) & r8 >> k & 1u) << k;
-    }
-    if (!__ballot(starts && cand != 0)) continue;   // no probe starts in this step
+    if (!__ballot(starts && s.cand != 0)) continue;   // no probe starts in this step: most steps of real data end here
     uint32_t run[4];    // valid bases from start k on, as far as the window goes
 #pragma unroll
     for (int k = 0; k < 4; ++k) run[k] = (uint32_t)__builtin_ctzll(~(uint64_t)val[k]);   // (WIDE: 32 when all are valid)
     for (int a = 0; a < pr.n; ++a) {
       if (found >> a & 1u) continue;
-      // probe a's length and code from lane a of pk / pc_lo / pc_hi (no scalar load in the loop)
-      const uint32_t K = (uint32_t)__builtin_amdgcn_readlane((int)pk, a);
-      const uint32_t code_lo = (uint32_t)__builtin_amdgcn_readlane((int)pc_lo, a);
+      // probe a's length and code from lane a of lp (no scalar load in the loop)
+      const uint32_t K = (uint32_t)__builtin_amdgcn_readlane((int)lp.len, a);
+      const uint32_t code_lo = (uint32_t)__builtin_amdgcn_readlane((int)lp.lo, a);
       uint32_t m = 0;
       if (WIDE) {
-        const uint64_t code = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)pc_hi, a) << 32 | code_lo;
+        const uint64_t code = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)lp.hi, a) << 32 | code_lo;
         const uint64_t mask = K == 32 ? ~0ull : (1ull << (2 * K)) - 1ull;
 #pragma unroll
         for (int k = 0; k < 4; ++k) m |= ((win[k] & mask) == code && run[k] >= K ? 1u : 0u) << k;
@@ -203,18 +142,10 @@ __global__ void __launch_bounds__(kWG) adapt_kernel(const char *seq, const int32
   __shared__ uint32_t bm[kBitmapWords];     // bit i: some probe's first 8 bases have the code bits i
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int i = threadIdx.x; i < pr.n * kP; i += kWG) t[i] = 0;
-  for (int i = threadIdx.x; i < kBitmapWords; i += kWG) bm[i] = 0;
-  __syncthreads();
-  if ((int)threadIdx.x < pr.n) {
-    const uint32_t ix8 = (uint32_t)pr.code[threadIdx.x] & 0xFFFFu;
-    atomicOr(&bm[ix8 >> 5], 1u << (ix8 & 31u));
-  }
-  __syncthreads();
+  probes::fill_bitmap<kWG>(bm, pr);   // (its first barrier covers t)
   const reads::Batch rd = reads::open<MASK>(seq, idx, n, mask);
   const int64_t ngroups = (n + kGroup - 1) / kGroup;
-  // lane a holds probe a: its code's halves and its length
-  const int pa = lane < pr.n ? lane : 0;
-  const uint32_t pc_lo = (uint32_t)pr.code[pa], pc_hi = (uint32_t)(pr.code[pa] >> 32), pk = pr.len[pa];
+  const probes::LaneProbe lp = probes::lane_probe(pr, lane);
   // over this wave's counted reads (wave-uniform)
   int longest = 0;
   uint32_t clipped = 0, nreads = 0, nany = 0;
@@ -224,37 +155,18 @@ __global__ void __launch_bounds__(kWG) adapt_kernel(const char *seq, const int32
     int32_t ix;
     uint32_t mk;
     reads::step_reads<kR, MASK>(rd, rb, n, lane, ix, mk);
-    // read i of the step: its first byte from the descriptor's base, its
-    // length, and whether it is scanned (counted, inside the rows, long enough)
-    auto first_load = [&](int i) {
-      const int32_t a = __builtin_amdgcn_readlane(ix, i);
-      const int32_t len = __builtin_amdgcn_readlane(ix, i + 1) - a;
-      const bool cnt = (uint32_t)__builtin_amdgcn_readlane((int)mk, i) == 1u;
-      const bool scan = cnt && len <= rows && len >= pr.kmin;
-      return reads::lane_load8(rd.bytes, (uint32_t)a + rd.shift, scan ? len : 0, lane);
-    };
-    v2u wq[kPre];
-#pragma unroll
-    for (int j = 0; j < kPre; ++j) wq[j] = first_load(j);
-    for (int i0 = 0; i0 < kR; i0 += kPre) {
-#pragma unroll
-      for (int j = 0; j < kPre; ++j) {
-        const int i = i0 + j;
-        const int32_t a = __builtin_amdgcn_readlane(ix, i);
-        const int32_t len = __builtin_amdgcn_readlane(ix, i + 1) - a;
-        const bool cnt = (uint32_t)__builtin_amdgcn_readlane((int)mk, i) == 1u;
-        const v2u w = wq[j];
-        if (i0 + kPre < kR) wq[j] = first_load(i + kPre);
-        if (!cnt) continue;   // (wave-uniform)
-        ++nreads;
-        longest = max(longest, len);
-        if (len > rows) {
-          ++clipped;
-          continue;
-        }
-        if (scan_read<WIDE>(rd.bytes, pr, lane, (uint32_t)a + rd.shift, len, w, pc_lo, pc_hi, pk, t, bm, first)) ++nany;
-      }
-    }
+    auto counted = [&](int i) { return (uint32_t)__builtin_amdgcn_readlane((int)mk, i) == 1u; };
+    reads::walk_reads<kR, kPre>(
+        rd, ix, lane,
+        // scanned: counted, inside the rows, long enough
+        [&](int i, int32_t len) { return counted(i) && len <= rows && len >= pr.kmin; },
+        [&](int i, int32_t a, int32_t len, v2u w) {
+          if (!counted(i)) return;   // (wave-uniform)
+          ++nreads;
+          longest = max(longest, len);
+          clipped += len > rows ? 1u : 0u;   // (a sum, not a branch of its own: the counters stay in registers)
+          if (len <= rows && scan_read<WIDE>(rd.bytes, pr, lane, (uint32_t)a + rd.shift, len, w, lp, t, bm, first)) ++nany;
+        });
   }
   __syncthreads();
   // flush: consecutive lanes take consecutive positions of one probe (a
@@ -304,24 +216,12 @@ int hpgq_adapt_open(hpgq_adapt_t **ad, int device, const char *const *probes, in
   if (!ad) return HPGQ_E_INVALID;
   *ad = nullptr;
   if (!probes || nprobes < 1 || nprobes > HPGQ_ADAPT_MAX_PROBES || rows < 1) return HPGQ_E_INVALID;
-  hpgq::adapt::Probes pr;
-  std::memset(&pr, 0, sizeof(pr));
-  pr.n = nprobes;
-  pr.kmin = HPGQ_ADAPT_MAX_LEN;
-  int kmax = 0;
-  for (int a = 0; a < nprobes; ++a) {
+  for (int a = 0; a < nprobes; ++a)
     if (hpgq_adapt_find(nullptr, 0, probes[a]) == -2) return HPGQ_E_INVALID;   // the probe rules
-    const int k = (int)std::strlen(probes[a]);
-    for (int j = 0; j < k; ++j) pr.code[a] |= (uint64_t)hpgq::adapt::code_of((unsigned char)probes[a][j]) << (2 * j);
-    pr.len[a] = (uint32_t)k;
-    pr.kmin = std::min(pr.kmin, k);
-    kmax = std::max(kmax, k);
-  }
   int rc = hpgq::accum::use_device(device);
   if (rc) return rc;
   hpgq_adapt *q = new hpgq_adapt;
-  q->pr = pr;
-  q->wide = kmax > hpgq::adapt::kNarrowMax;
+  q->wide = hpgq::probes::encode(q->pr, probes, nprobes);
   if ((rc = q->open(device, stream, rows, kRowBytes, 2)) != HPGQ_OK) {
     hpgq_adapt_close(q);
     return rc;

@@ -12,11 +12,10 @@
 //   clip_copy_kernel   sequence and quality [idx[i], idx[i] + c_i) to
 //                      [idx_out[i], idx_out[i + 1]).
 //
-// Find.  The step is hpgq_adapt.hip's (a wave takes kR = 16 reads, one after the
-// other; lane l takes the read's bytes p0 + 4l .. p0 + 4l + 3, packed into 2-bit
-// codes and validity bits, windows built across lanes with ds_bpermute; the
-// workgroup's bitmap of the set's 8-base prefixes ends most steps after one
-// ballot), with these differences:
+// Find.  A wave takes kR = 16 reads, one after the other (hpgq_reads.h); the
+// step -- codes and validity bits, the windows across lanes, the bitmap of the
+// set's 8-base prefixes that ends most steps after one ballot -- is
+// hpgq_probes.h's, shared with hpgq_adapt.hip.  What differs from adapt:
 //   * a read ends at its first hit.  A step with candidates walks them, lowest
 //     start first: the start's window goes to every lane (v_readlane), lane a
 //     compares probe a (the probe parameters already sit in lanes 0 .. 31), and
@@ -32,108 +31,71 @@
 //     hit gets one more load of its last 7 bytes; lane a compares probe a, one
 //     ballot per start.
 //
-// Scan and copy: hpgq_cut.h, shared with hpgq_ovl.hip.
+// Scan and copy, and what the handle owns beyond its own state: hpgq_cut.h,
+// shared with hpgq_ovl.hip.
 #include "hpgq_accum.h"
 #include "hpgq_cut.h"
+#include "hpgq_probes.h"
 #include "hpgq_reads.h"
 
 #include <algorithm>
-#include <cstring>
 
 namespace hpgq {
 namespace clip {
 
-constexpr int kMaxProbes = HPGQ_ADAPT_MAX_PROBES;
 constexpr int kWG = 512;
 constexpr int kWaves = kWG / 64;
 constexpr int kR = 16;      // reads per wave step
 constexpr int kPre = 4;     // of them with their first load in flight
 constexpr int kGroup = kWaves * kR;   // reads per workgroup step
-constexpr int kNarrowMax = 13;        // longest probe of the 32-bit window: 16 bases less the 3 a start may skip
-constexpr int kPrefix = 8;            // bases of the prefilter: HPGQ_ADAPT_MIN_LEN
-constexpr int kBitmapWords = 65536 / 32;   // one bit per 8-base prefix (16 code bits)
-constexpr int kScalars = 3 + kMaxProbes;   // reads, clipped, bases_removed, by_probe[32]
+using probes::kBitmapWords;
+using probes::kMaxProbes;
+using probes::kPrefix;
+using probes::Probes;
 using reads::v2u;
-using reads::pack4;
-using reads::lane_bytes;
-static_assert(kR % kPre == 0, "the reads of a wave step go in blocks of kPre");
-static_assert(kPrefix == HPGQ_ADAPT_MIN_LEN, "every probe has the prefilter's bases");
-
-// the probe set as the kernel takes it (by value: scalar loads)
-struct Probes {
-  uint64_t code[kMaxProbes];   // base j at bits 2j .. 2j + 1
-  uint32_t len[kMaxProbes];
-  int32_t n, kmin, min_ov;
-};
-
-// the 2-bit code of an A C G T byte
-__host__ __device__ inline uint32_t code_of(uint32_t b) { return (b >> 1) & 3u; }
-
-__device__ __forceinline__ uint32_t pull(uint32_t v, int lane, int d) {
-  return (uint32_t)__builtin_amdgcn_ds_bpermute(((lane + d) & 63) * 4, (int)v);
-}
+constexpr int kScalars = 3 + kMaxProbes;   // reads, clipped, bases_removed, by_probe[32]
 
 // One read of len bytes at st0 (from the descriptor's base); w0: its first
-// step's load.  Everything but the lane's bytes is wave-uniform.  -> c, and the
-// winning probe in `who` (0xFF: none).
+// step's load; lp: lane a's probe a.  Everything but the lane's bytes is
+// wave-uniform.  -> c, and the winning probe in `who` (0xFF: none).
 template <bool WIDE>
-__device__ __forceinline__ int find_read(const __amdgpu_buffer_rsrc_t rq, const Probes &pr, int lane, uint32_t st0, int len,
-                                         v2u w0, uint32_t pc_lo, uint32_t pc_hi, uint32_t pk, const uint32_t *bm,
+__device__ __forceinline__ int find_read(const __amdgpu_buffer_rsrc_t rq, const Probes &pr, int min_ov, int lane,
+                                         uint32_t st0, int len, v2u w0, const probes::LaneProbe lp, const uint32_t *bm,
                                          uint32_t &who) {
   constexpr int H = WIDE ? 8 : 3;          // lanes after its own a lane's windows reach into
   constexpr int S = 4 * (64 - H);          // starts per step
   // the fewest bases a match of the steps compares: a whole probe, or an overlap that passes the prefilter
-  const int least = min(pr.kmin, max(pr.min_ov, kPrefix));
+  const int least = min(pr.kmin, max(min_ov, kPrefix));
   for (int p0 = 0; p0 + least <= len; p0 += S) {
     const int rem = len - p0;
     const uint32_t st = st0 + (uint32_t)p0;
     const v2u w = p0 == 0 ? w0 : reads::lane_load8(rq, st, rem, lane);
-    uint32_t c, ok;
-    pack4(lane_bytes(w, st, rem, lane), c, ok);
-    // 16 bases from lanes l .. l + 3: codes 32 bits, validity 16
-    const uint32_t x1 = c | ok << 8;
-    const uint32_t y1 = pull(x1, lane, 1);
-    const uint32_t c2 = c | (y1 & 0xFFu) << 8, ok2 = ok | (y1 >> 8 & 0xFu) << 4;
-    const uint32_t y2 = pull(c2 | ok2 << 16, lane, 2);
-    const uint32_t c4 = c2 | y2 << 16, ok4 = ok2 | (y2 >> 16 & 0xFFu) << 8;
-    // Prefilter: a match of the steps compares at least 8 bases, so it can start
-    // only where the next 8 bases are valid (r8) and their 16 code bits are the
-    // first 8 bases of some probe (one bit of bm).  The lane's own 16 bases
-    // decide that, whatever the probes' lengths.
+    // 16 bases from lanes l .. l + 3 and the prefilter: a match of the steps
+    // compares at least 8 bases, so it starts at a candidate
+    const probes::Window s = probes::window(w, st, rem, lane, bm);
     const bool starts = lane < 64 - H;   // the last H lanes only supply bases
-    const uint32_t r2 = ok4 & ok4 >> 1, r4 = r2 & r2 >> 2, r8 = r4 & r4 >> 4;
-    uint32_t cand = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const uint32_t ix8 = c4 >> (2 * k) & 0xFFFFu;
-      cand |= (bm[ix8 >> 5] >> (ix8 & 31u) & r8 >> k & 1u) << k;
-    }
-    unsigned long long lanes = __ballot(starts && cand != 0);
+    unsigned long long lanes = __ballot(starts && s.cand != 0);
     if (!lanes) continue;   // nothing starts in this step
     // WIDE: the bases of lanes l + 4 .. l + 8 behind the lane's 16 (only a step with a candidate needs them)
-    uint32_t c8_hi = 0, ok8_hi = 0, y9 = 0;
-    if (WIDE) {
-      c8_hi = pull(c4, lane, 4);
-      ok8_hi = pull(ok4, lane, 4);
-      y9 = pull(x1, lane, 8);
-    }
+    probes::Wide x{0, 0, 0};
+    if (WIDE) x = probes::pull_wide(s, lane);
     // The candidates, lowest first: the window of one start goes to every lane,
     // lane a compares probe a, and one ballot gives the lowest probe that matches
     // there.  The first start with a match is c.
     do {
       const int l0 = __builtin_ctzll(lanes);
-      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)c4, l0);
-      const uint32_t vlo = (uint32_t)__builtin_amdgcn_readlane((int)ok4, l0);
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)s.c4, l0);
+      const uint32_t vlo = (uint32_t)__builtin_amdgcn_readlane((int)s.ok4, l0);
       uint64_t base = lo;          // the bases from the lane's first on, 2 bits each (WIDE: 32 and 4 more in over)
       uint32_t valid = vlo, over = 0, vover = 0;
       if (WIDE) {
-        base |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)c8_hi, l0) << 32;
-        valid |= (uint32_t)__builtin_amdgcn_readlane((int)ok8_hi, l0) << 16;
-        const uint32_t y = (uint32_t)__builtin_amdgcn_readlane((int)y9, l0);
+        base |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)x.c8_hi, l0) << 32;
+        valid |= (uint32_t)__builtin_amdgcn_readlane((int)x.ok8_hi, l0) << 16;
+        const uint32_t y = (uint32_t)__builtin_amdgcn_readlane((int)x.y9, l0);
         over = y & 0xFFu;
         vover = y >> 8 & 0xFu;
       }
-      for (uint32_t ks = (uint32_t)__builtin_amdgcn_readlane((int)cand, l0); ks; ks &= ks - 1u) {
+      for (uint32_t ks = (uint32_t)__builtin_amdgcn_readlane((int)s.cand, l0); ks; ks &= ks - 1u) {
         const int k0 = __builtin_ctz(ks);
         const uint64_t win = WIDE && k0 ? base >> (2 * k0) | (uint64_t)over << (64 - 2 * k0) : base >> (2 * k0);
         const uint32_t val = WIDE && k0 ? valid >> k0 | vover << (32 - k0) : valid >> k0;
@@ -142,16 +104,16 @@ __device__ __forceinline__ int find_read(const __amdgpu_buffer_rsrc_t rq, const 
         const uint32_t run = (uint32_t)__builtin_ctzll(~(uint64_t)val);
         const uint32_t left = (uint32_t)min(rem - 4 * l0 - k0, 32);
         // lane a: probe a's whole length, or what the read has left of it (8 or more: the start is a candidate)
-        const uint32_t cmp = min(pk, left);
+        const uint32_t cmp = min(lp.len, left);
         bool eq;
         if (WIDE) {
           const uint64_t mask = cmp >= 32u ? ~0ull : (1ull << (2 * cmp)) - 1ull;
-          eq = ((win ^ ((uint64_t)pc_hi << 32 | pc_lo)) & mask) == 0;
+          eq = ((win ^ ((uint64_t)lp.hi << 32 | lp.lo)) & mask) == 0;
         } else {
-          eq = (((uint32_t)win ^ pc_lo) & ((1u << (2 * cmp)) - 1u)) == 0;
+          eq = (((uint32_t)win ^ lp.lo) & ((1u << (2 * cmp)) - 1u)) == 0;
         }
         const unsigned long long hit =
-            __ballot(lane < pr.n && eq && run >= cmp && (cmp == pk || cmp >= (uint32_t)pr.min_ov));
+            __ballot(lane < pr.n && eq && run >= cmp && (cmp == lp.len || cmp >= (uint32_t)min_ov));
         if (hit) {
           who = (uint32_t)__builtin_ctzll(hit);
           return p0 + 4 * l0 + k0;
@@ -162,17 +124,17 @@ __device__ __forceinline__ int find_read(const __amdgpu_buffer_rsrc_t rq, const 
   }
   // Overlaps of fewer than 8 bases: the read's last tn <= 7 bytes, all of which
   // lie behind every start the steps above can hit.  Lane a holds probe a.
-  if (pr.min_ov < kPrefix && len >= pr.min_ov) {
+  if (min_ov < kPrefix && len >= min_ov) {
     const int ts = max(len - (kPrefix - 1), 0), tn = len - ts;
     const uint32_t st = st0 + (uint32_t)ts;
     uint32_t c, ok;
-    pack4(lane_bytes(reads::lane_load8(rq, st, tn, lane), st, tn, lane), c, ok);
+    reads::pack4(reads::lane_bytes(reads::lane_load8(rq, st, tn, lane), st, tn, lane), c, ok);
     const uint32_t tc = (uint32_t)__builtin_amdgcn_readlane((int)c, 0) | (uint32_t)__builtin_amdgcn_readlane((int)c, 1) << 8;
     const uint32_t tok = (uint32_t)__builtin_amdgcn_readlane((int)ok, 0) | (uint32_t)__builtin_amdgcn_readlane((int)ok, 1) << 4;
-    for (int d = 0; tn - d >= pr.min_ov; ++d) {
+    for (int d = 0; tn - d >= min_ov; ++d) {
       const int m = tn - d;   // 1 .. 7 bases, fewer than any probe has
       const uint32_t vm = (1u << m) - 1u, cm = (1u << (2 * m)) - 1u;
-      const bool eq = lane < pr.n && (tok >> d & vm) == vm && ((tc >> (2 * d) ^ pc_lo) & cm) == 0;
+      const bool eq = lane < pr.n && (tok >> d & vm) == vm && ((tc >> (2 * d) ^ lp.lo) & cm) == 0;
       const unsigned long long hit = __ballot(eq);
       if (hit) {
         who = (uint32_t)__builtin_ctzll(hit);
@@ -187,25 +149,18 @@ __device__ __forceinline__ int find_read(const __amdgpu_buffer_rsrc_t rq, const 
 // WIDE: a probe longer than kNarrowMax (a compile-time choice)
 template <bool WIDE>
 __global__ void __launch_bounds__(kWG) clip_find_kernel(const char *seq, const int32_t *idx, int64_t n, const Probes pr,
-                                                        uint32_t *pos_out, uint8_t *probe_out, unsigned long long *scal) {
+                                                        int min_ov, uint32_t *pos_out, uint8_t *probe_out,
+                                                        unsigned long long *scal) {
   __shared__ uint32_t bm[kBitmapWords];     // bit i: some probe's first 8 bases have the code bits i
   __shared__ uint32_t won[kMaxProbes];      // reads won per probe
   __shared__ unsigned long long red[3 * kWaves];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int i = threadIdx.x; i < kBitmapWords; i += kWG) bm[i] = 0;
   if (threadIdx.x < kMaxProbes) won[threadIdx.x] = 0;
-  __syncthreads();
-  if ((int)threadIdx.x < pr.n) {
-    const uint32_t ix8 = (uint32_t)pr.code[threadIdx.x] & 0xFFFFu;
-    atomicOr(&bm[ix8 >> 5], 1u << (ix8 & 31u));
-  }
-  __syncthreads();
+  probes::fill_bitmap<kWG>(bm, pr);   // (its first barrier covers won)
   const reads::Batch rd = reads::open<false>(seq, idx, n, nullptr);
   const int64_t ngroups = (n + kGroup - 1) / kGroup;
-  // lane a holds probe a: its code's halves and its length
-  const int pa = lane < pr.n ? lane : 0;
-  const uint32_t pc_lo = (uint32_t)pr.code[pa], pc_hi = (uint32_t)(pr.code[pa] >> 32), pk = pr.len[pa];
-  const int shortest = min(pr.kmin, pr.min_ov);   // a shorter read has no match
+  const probes::LaneProbe lp = probes::lane_probe(pr, lane);
+  const int shortest = min(pr.kmin, min_ov);   // a shorter read has no match
   // over this wave's reads (wave-uniform; a launch has at most 2^28 reads and 2^31 bytes)
   uint32_t nreads = 0, nclipped = 0, removed = 0;
   for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
@@ -214,43 +169,28 @@ __global__ void __launch_bounds__(kWG) clip_find_kernel(const char *seq, const i
     int32_t ix;
     uint32_t mk;
     reads::step_reads<kR, false>(rd, rb, n, lane, ix, mk);
-    auto first_load = [&](int i) {
-      const int32_t a = __builtin_amdgcn_readlane(ix, i);
-      const int32_t len = __builtin_amdgcn_readlane(ix, i + 1) - a;
-      const bool scan = (uint32_t)__builtin_amdgcn_readlane((int)mk, i) == 1u && len >= shortest;
-      return reads::lane_load8(rd.bytes, (uint32_t)a + rd.shift, scan ? len : 0, lane);
-    };
-    v2u wq[kPre];
-#pragma unroll
-    for (int j = 0; j < kPre; ++j) wq[j] = first_load(j);
     nreads += (uint32_t)(n - rb < kR ? n - rb : kR);
     // lane i: read i's result.  A read without a hit keeps its length and no
     // winner, so only a hit costs the wave anything here.
-    int my_c = (int)pull((uint32_t)ix, lane, 1) - ix, my_who = 0xFF;
-    for (int i0 = 0; i0 < kR; i0 += kPre) {
-#pragma unroll
-      for (int j = 0; j < kPre; ++j) {
-        const int i = i0 + j;
-        const int32_t a = __builtin_amdgcn_readlane(ix, i);
-        const int32_t len = __builtin_amdgcn_readlane(ix, i + 1) - a;
-        const bool on = (uint32_t)__builtin_amdgcn_readlane((int)mk, i) == 1u;
-        const v2u w = wq[j];
-        if (i0 + kPre < kR) wq[j] = first_load(i + kPre);
-        if (!on) continue;   // past the batch (wave-uniform)
-        uint32_t who = 0xFFu;
-        int c = len;
-        if (len >= shortest) c = find_read<WIDE>(rd.bytes, pr, lane, (uint32_t)a + rd.shift, len, w, pc_lo, pc_hi, pk, bm, who);
-        if (c < len) {
-          ++nclipped;
-          removed += (uint32_t)(len - c);
-          if (lane == 0) atomicAdd(&won[who], 1u);
-          if (lane == i) {
-            my_c = c;
-            my_who = (int)who;
+    int my_c = (int)probes::pull((uint32_t)ix, lane, 1) - ix, my_who = 0xFF;
+    auto on = [&](int i) { return (uint32_t)__builtin_amdgcn_readlane((int)mk, i) == 1u; };
+    reads::walk_reads<kR, kPre>(
+        rd, ix, lane, [&](int i, int32_t len) { return on(i) && len >= shortest; },
+        [&](int i, int32_t a, int32_t len, v2u w) {
+          if (!on(i)) return;   // past the batch (wave-uniform)
+          uint32_t who = 0xFFu;
+          int c = len;
+          if (len >= shortest) c = find_read<WIDE>(rd.bytes, pr, min_ov, lane, (uint32_t)a + rd.shift, len, w, lp, bm, who);
+          if (c < len) {
+            ++nclipped;
+            removed += (uint32_t)(len - c);
+            if (lane == 0) atomicAdd(&won[who], 1u);
+            if (lane == i) {
+              my_c = c;
+              my_who = (int)who;
+            }
           }
-        }
-      }
-    }
+        });
     if (lane < kR && rb + lane < n) {
       pos_out[rb + lane] = (uint32_t)my_c;
       if (probe_out) probe_out[rb + lane] = (uint8_t)my_who;
@@ -275,28 +215,13 @@ __global__ void __launch_bounds__(kWG) clip_find_kernel(const char *seq, const i
 }  // namespace clip
 }  // namespace hpgq
 
-struct hpgq_clip {
-  int device = 0;
-  hpgq::accum::Stream stream;
-  hpgq::accum::Retired retired;             // owned buffers replaced by larger ones
-  hpgq::clip::Probes pr;
+// the scalars: [reads, clipped, bases_removed, by_probe[32]]
+struct hpgq_clip : hpgq::cut::Cutter {
+  hpgq::probes::Probes pr;
   bool wide = false;
-  unsigned long long *d_scal = nullptr;     // [kScalars]
-  unsigned long long *h_scal = nullptr;     // pinned: the scalars, then the two offsets hpgq_clip_batch_device fetches
-  int cus = 0, max_wg = 0;
-  hpgq::cut::Scan scan;                     // the scan's temporary storage
+  int min_ov = 0;
   hpgq::cut::Positions pos;                 // positions when the caller wants none
   hpgq::cut::Kept kept;                     // hpgq_clip_batch_device's outputs
-
-  hpgq::cut::Ctx ctx() { return hpgq::cut::Ctx{stream, &retired, cus, max_wg}; }
-
-  int settle() {
-    HPGQ_HIP_TRY(hipSetDevice(device));
-    HPGQ_HIP_TRY(hipMemcpyAsync(h_scal, d_scal, hpgq::clip::kScalars * 8, hipMemcpyDeviceToHost, stream));
-    HPGQ_HIP_TRY(hipStreamSynchronize(stream));
-    retired.free_all();
-    return HPGQ_OK;
-  }
 };
 
 namespace {
@@ -309,10 +234,10 @@ int find(hpgq_clip *q, const hpgq_batch_t *b, uint32_t *pos, uint8_t *probe) {
   return hpgq::accum::for_parts(b, nullptr, [&](const int32_t *ix, const uint8_t *, int64_t n) {
     const int64_t lo = ix - b->data_indices;
     // four workgroups of 512 threads per CU stay resident (8.6 KB of LDS each)
-    const dim3 grid(q->ctx().grid(4, (n + kGroup - 1) / kGroup));
+    const dim3 grid(q->grid(4, (n + kGroup - 1) / kGroup));
     auto *k = q->wide ? clip_find_kernel<true> : clip_find_kernel<false>;
-    hipLaunchKernelGGL(k, grid, dim3(kWG), 0, q->stream, b->seq, ix, n, q->pr, pos + lo, probe ? probe + lo : nullptr,
-                       q->d_scal);
+    hipLaunchKernelGGL(k, grid, dim3(kWG), 0, q->stream, b->seq, ix, n, q->pr, q->min_ov, pos + lo,
+                       probe ? probe + lo : nullptr, q->d_scal);
   });
 }
 
@@ -324,33 +249,12 @@ int hpgq_clip_open(hpgq_clip_t **cl, int device, const char *const *probes, int 
   if (!cl) return HPGQ_E_INVALID;
   *cl = nullptr;
   if (hpgq_clip_find(nullptr, 0, probes, nprobes, min_overlap, nullptr) == -2) return HPGQ_E_INVALID;   // the rules of §2.12
-  Probes pr;
-  std::memset(&pr, 0, sizeof(pr));
-  pr.n = nprobes;
-  pr.kmin = HPGQ_ADAPT_MAX_LEN;
-  pr.min_ov = min_overlap;
-  int kmax = 0;
-  for (int a = 0; a < nprobes; ++a) {
-    const int k = (int)std::strlen(probes[a]);
-    for (int j = 0; j < k; ++j) pr.code[a] |= (uint64_t)code_of((unsigned char)probes[a][j]) << (2 * j);
-    pr.len[a] = (uint32_t)k;
-    pr.kmin = std::min(pr.kmin, k);
-    kmax = std::max(kmax, k);
-  }
   int rc = hpgq::accum::use_device(device);
   if (rc) return rc;
   hpgq_clip *q = new hpgq_clip;
-  q->device = device;
-  q->pr = pr;
-  q->wide = kmax > kNarrowMax;
-  rc = q->stream.open(stream);
-  if (rc == HPGQ_OK && (hipMalloc(reinterpret_cast<void **>(&q->d_scal), kScalars * 8) != hipSuccess ||
-                        hipHostMalloc(reinterpret_cast<void **>(&q->h_scal), kScalars * 8 + 8, hipHostMallocDefault) != hipSuccess))
-    rc = HPGQ_E_NOMEM;
-  if (rc == HPGQ_OK && (hipMemsetAsync(q->d_scal, 0, kScalars * 8, q->stream) != hipSuccess ||
-                        hipDeviceGetAttribute(&q->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess))
-    rc = HPGQ_E_HIP;
-  if (rc) {
+  q->wide = hpgq::probes::encode(q->pr, probes, nprobes);
+  q->min_ov = min_overlap;
+  if ((rc = q->open(device, stream, kScalars)) != HPGQ_OK) {
     hpgq_clip_close(q);
     return rc;
   }
@@ -360,15 +264,9 @@ int hpgq_clip_open(hpgq_clip_t **cl, int device, const char *const *probes, int 
 
 void hpgq_clip_close(hpgq_clip_t *q) {
   if (!q) return;
-  (void)hipSetDevice(q->device);
-  if (q->stream) (void)hipStreamSynchronize(q->stream);
-  q->retired.free_all();
-  (void)hipFree(q->d_scal);
-  q->scan.free();
+  q->close();
   q->pos.free();
   q->kept.free();
-  if (q->h_scal) (void)hipHostFree(q->h_scal);
-  q->stream.close();
   delete q;
 }
 
@@ -386,19 +284,19 @@ int hpgq_clip_device(hpgq_clip_t *q, const hpgq_batch_t *b, char *seq_out, char 
   if (b->num_reads && (!b->quality || !seq_out || !qual_out)) return HPGQ_E_INVALID;
   HPGQ_HIP_TRY(hipSetDevice(q->device));
   if (!pos_out && b->num_reads) {
-    const int rc = q->pos.need(q->ctx(), b->num_reads);
+    const int rc = q->pos.need(*q, b->num_reads);
     if (rc) return rc;
     pos_out = q->pos.d;
   }
   const int rc = b->num_reads ? find(q, b, pos_out, probe_out) : HPGQ_OK;
-  return rc ? rc : hpgq::cut::scan_and_copy(q->ctx(), q->scan, b, pos_out, seq_out, qual_out, idx_out);
+  return rc ? rc : hpgq::cut::scan_and_copy(*q, b, pos_out, seq_out, qual_out, idx_out);
 }
 
 int hpgq_clip_batch_device(hpgq_clip_t *q, const hpgq_batch_t *in, hpgq_batch_t *out) {
   if (!q || !batch_ok(in) || !out || (in->num_reads && !in->quality)) return HPGQ_E_INVALID;
   HPGQ_HIP_TRY(hipSetDevice(q->device));
   const hpgq_batch_t b = *in;   // (in and out may be the same struct)
-  int rc = q->kept.reserve(q->ctx(), b, reinterpret_cast<int32_t *>(q->h_scal + kScalars));
+  int rc = q->kept.reserve(*q, b);
   if (rc) return rc;
   rc = hpgq_clip_device(q, &b, q->kept.o_seq, q->kept.o_qual, q->kept.o_idx, nullptr, nullptr);
   if (rc) return rc;
@@ -408,12 +306,7 @@ int hpgq_clip_batch_device(hpgq_clip_t *q, const hpgq_batch_t *in, hpgq_batch_t 
 
 int hpgq_clip_sync(hpgq_clip_t *q) { return q ? q->settle() : HPGQ_E_INVALID; }
 
-int hpgq_clip_reset(hpgq_clip_t *q) {
-  if (!q) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  HPGQ_HIP_TRY(hipMemsetAsync(q->d_scal, 0, kScalars * 8, q->stream));
-  return HPGQ_OK;
-}
+int hpgq_clip_reset(hpgq_clip_t *q) { return q ? q->reset() : HPGQ_E_INVALID; }
 
 int hpgq_clip_read(hpgq_clip_t *q, hpgq_clip_info_t *info) {
   if (!q || !info) return HPGQ_E_INVALID;
@@ -424,14 +317,12 @@ int hpgq_clip_read(hpgq_clip_t *q, hpgq_clip_info_t *info) {
   info->bases_removed = q->h_scal[2];
   for (int a = 0; a < kMaxProbes; ++a) info->by_probe[a] = q->h_scal[3 + a];
   info->nprobes = q->pr.n;
-  info->min_overlap = q->pr.min_ov;
+  info->min_overlap = q->min_ov;
   return HPGQ_OK;
 }
 
 int hpgq_clip_debug_set_max_workgroups(hpgq_clip_t *q, int max_wg) {
-  if (!q || max_wg < 0) return HPGQ_E_INVALID;
-  q->max_wg = max_wg;
-  return HPGQ_OK;
+  return q ? q->set_max_workgroups(max_wg) : HPGQ_E_INVALID;
 }
 
 }  // extern "C"

@@ -18,6 +18,10 @@
 //
 // The kernels are static: every handle's translation unit holds its own copy of
 // the code, none of them a second implementation.
+//
+// The handles derive from Cutter: the stream, the replaced buffers, the
+// scalars and the grid limits are accum::Handle's (hpgq_accum.h, DESIGN.md
+// §4.14), as for the counters per read position.
 #pragma once
 #include "hpgq_accum.h"
 #include "hpgq_reads.h"
@@ -107,26 +111,31 @@ static __global__ void clip_carry_kernel(int32_t *out, int64_t n, const int32_t 
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) out[i] += c;
 }
 
-// What the cut takes from its handle: the stream, the list of replaced buffers
-// and the grid limits.
-struct Ctx {
-  hipStream_t stream;
-  accum::Retired *retired;
-  int cus, max_wg;
+// a device buffer of at least `want` units in place of *p, the old one retired
+template <class T>
+int grow(accum::Handle &h, T **p, size_t unit, size_t want, bool zero) {
+  T *d = nullptr;
+  if (hipMalloc(reinterpret_cast<void **>(&d), want * unit) != hipSuccess) return HPGQ_E_NOMEM;
+  if (zero) HPGQ_HIP_TRY(hipMemsetAsync(d, 0, want * unit, h.stream));
+  if (*p) h.retired.add(*p);
+  *p = d;
+  return HPGQ_OK;
+}
 
-  unsigned grid(int64_t per_cu, int64_t groups) const {
-    return (unsigned)accum::capped(std::min<int64_t>(per_cu * (int64_t)std::max(1, cus), groups), max_wg);
-  }
+// the scan's temporary storage
+struct Scan {
+  char *d_tmp = nullptr;
+  size_t tmp_bytes = 0;
+  void free() { (void)hipFree(d_tmp); }
+};
 
-  // a device buffer of at least `want` units in place of *p, the old one retired
-  template <class T>
-  int grow(T **p, size_t unit, size_t want, bool zero) const {
-    T *d = nullptr;
-    if (hipMalloc(reinterpret_cast<void **>(&d), want * unit) != hipSuccess) return HPGQ_E_NOMEM;
-    if (zero) HPGQ_HIP_TRY(hipMemsetAsync(d, 0, want * unit, stream));
-    if (*p) retired->add(*p);
-    *p = d;
-    return HPGQ_OK;
+// What every handle that cuts owns: accum::Handle's (its pinned extra word:
+// the two offsets Kept::reserve fetches) and the scan's storage.
+struct Cutter : accum::Handle {
+  Scan scan;
+  void close() {
+    accum::Handle::close();
+    scan.free();
   }
 };
 
@@ -138,26 +147,20 @@ inline bool batch_ok(const hpgq_batch_t *b) {
 struct Positions {
   uint32_t *d = nullptr;
   int64_t cap = 0;
-  int need(const Ctx &c, int64_t n) {
+  int need(accum::Handle &h, int64_t n) {
     if (n <= cap) return HPGQ_OK;
     const int64_t want = std::max<int64_t>(n, cap + cap / 2);
-    const int rc = c.grow(&d, 4, (size_t)want, false);
+    const int rc = grow(h, &d, 4, (size_t)want, false);
     if (rc == HPGQ_OK) cap = want;
     return rc;
   }
   void free() { (void)hipFree(d); }
 };
 
-// the scan's temporary storage
-struct Scan {
-  char *d_tmp = nullptr;
-  size_t tmp_bytes = 0;
-  void free() { (void)hipFree(d_tmp); }
-};
-
 // idx_out[0] = 0, idx_out[i + 1] = idx_out[i] + pos[i], then the copy; async
-inline int scan_and_copy(const Ctx &c, Scan &s, const hpgq_batch_t *b, const uint32_t *pos, char *seq_out, char *qual_out,
+inline int scan_and_copy(Cutter &c, const hpgq_batch_t *b, const uint32_t *pos, char *seq_out, char *qual_out,
                          int32_t *idx_out) {
+  Scan &s = c.scan;
   HPGQ_HIP_TRY(hipMemsetAsync(idx_out, 0, 4, c.stream));
   if (b->num_reads == 0) return HPGQ_OK;
   const int first = (int)std::min<int64_t>(b->num_reads, accum::kPart);
@@ -165,7 +168,7 @@ inline int scan_and_copy(const Ctx &c, Scan &s, const hpgq_batch_t *b, const uin
   HPGQ_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, reinterpret_cast<const int32_t *>(pos), idx_out + 1, first,
                                                 c.stream));
   if (tb > s.tmp_bytes) {
-    const int rc = c.grow(&s.d_tmp, 1, tb, false);
+    const int rc = grow(c, &s.d_tmp, 1, tb, false);
     if (rc) return rc;
     s.tmp_bytes = tb;
   }
@@ -190,9 +193,10 @@ struct Kept {
   int64_t o_reads = -1;
 
   // Room for what b can keep at most: its bytes (its first and last offset live
-  // on the device: fetched through the two pinned words `ends`, one wait for
+  // on the device: fetched through the handle's pinned extra word, one wait for
   // the stream) and its reads.
-  int reserve(const Ctx &c, const hpgq_batch_t &b, int32_t *ends) {
+  int reserve(accum::Handle &c, const hpgq_batch_t &b) {
+    int32_t *const ends = static_cast<int32_t *>(c.h_extra());
     size_t bytes = 0;
     if (b.num_reads) {
       HPGQ_HIP_TRY(hipMemcpyAsync(ends, b.data_indices, 4, hipMemcpyDeviceToHost, c.stream));
@@ -203,14 +207,14 @@ struct Kept {
     }
     if (!o_seq || bytes > o_bytes) {
       const size_t cap = std::max(bytes, o_bytes + o_bytes / 2);
-      int rc = c.grow(&o_seq, 1, cap + HPGQ_DEVICE_SLACK, true);
-      if (rc == HPGQ_OK) rc = c.grow(&o_qual, 1, cap + HPGQ_DEVICE_SLACK, true);
+      int rc = grow(c, &o_seq, 1, cap + HPGQ_DEVICE_SLACK, true);
+      if (rc == HPGQ_OK) rc = grow(c, &o_qual, 1, cap + HPGQ_DEVICE_SLACK, true);
       if (rc) return rc;
       o_bytes = cap;
     }
     if (b.num_reads > o_reads) {
       const int64_t cap = std::max<int64_t>(b.num_reads, o_reads + o_reads / 2);
-      const int rc = c.grow(&o_idx, 4, (size_t)cap + 1, false);
+      const int rc = grow(c, &o_idx, 4, (size_t)cap + 1, false);
       if (rc) return rc;
       o_reads = cap;
     }

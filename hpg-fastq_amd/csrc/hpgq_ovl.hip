@@ -8,6 +8,10 @@
 //                      sequence bytes and offsets.
 //   scan and copy      hpgq_cut.h, once per mate: the kept reads back to back.
 //
+// What the handle owns beyond its own state (stream, scalars, replaced buffers,
+// grid limits, the scan's storage) is hpgq_cut.h's Cutter, shared with
+// hpgq_clip.hip.
+//
 // Find.  A wave takes kR = 16 pairs, one after the other (the read step of
 // hpgq_reads.h on both batches).  A pair with a mate of fewer than min_overlap
 // bases has no candidate and costs nothing more.  Otherwise lane l packs the
@@ -157,27 +161,11 @@ __global__ void __launch_bounds__(kWG) ovl_find_kernel(const char *seq1, const i
 }  // namespace ovl
 }  // namespace hpgq
 
-struct hpgq_ovl {
-  int device = 0;
-  hpgq::accum::Stream stream;
-  hpgq::accum::Retired retired;             // owned buffers replaced by larger ones
+// the scalars: [pairs, skipped, overlapping, clipped, bases_removed[2]]
+struct hpgq_ovl : hpgq::cut::Cutter {
   int min_ov = 0, max_mm = 0;
-  unsigned long long *d_scal = nullptr;     // [kScalars]
-  unsigned long long *h_scal = nullptr;     // pinned: the scalars, then the two offsets hpgq_ovl_batch_device fetches
-  int cus = 0, max_wg = 0;
-  hpgq::cut::Scan scan;                     // the scan's temporary storage
   hpgq::cut::Positions pos[2];              // hpgq_ovl_batch_device's positions, per mate
   hpgq::cut::Kept kept[2];                  // and its outputs
-
-  hpgq::cut::Ctx ctx() { return hpgq::cut::Ctx{stream, &retired, cus, max_wg}; }
-
-  int settle() {
-    HPGQ_HIP_TRY(hipSetDevice(device));
-    HPGQ_HIP_TRY(hipMemcpyAsync(h_scal, d_scal, hpgq::ovl::kScalars * 8, hipMemcpyDeviceToHost, stream));
-    HPGQ_HIP_TRY(hipStreamSynchronize(stream));
-    retired.free_all();
-    return HPGQ_OK;
-  }
 };
 
 namespace {
@@ -191,16 +179,14 @@ bool pair_ok(const hpgq_batch_t *m1, const hpgq_batch_t *m2) {
 
 // the find pass over the pairs, async; every output may be null
 int find(hpgq_ovl *q, const hpgq_batch_t *m1, const hpgq_batch_t *m2, int32_t *ins, uint32_t *pos1, uint32_t *pos2) {
-  for (int64_t lo = 0; lo < m1->num_reads; lo += hpgq::accum::kPart) {
-    const int64_t n = std::min(hpgq::accum::kPart, m1->num_reads - lo);
+  return hpgq::accum::for_parts(m1, nullptr, [&](const int32_t *ix1, const uint8_t *, int64_t n) {
+    const int64_t lo = ix1 - m1->data_indices;
     // four workgroups of 512 threads per CU stay resident (5.5 KB of LDS each)
-    const dim3 grid(q->ctx().grid(4, (n + kGroup - 1) / kGroup));
-    hipLaunchKernelGGL(ovl_find_kernel, grid, dim3(kWG), 0, q->stream, m1->seq, m1->data_indices + lo, m2->seq,
-                       m2->data_indices + lo, n, q->min_ov, q->max_mm, ins ? ins + lo : nullptr, pos1 ? pos1 + lo : nullptr,
+    const dim3 grid(q->grid(4, (n + kGroup - 1) / kGroup));
+    hipLaunchKernelGGL(ovl_find_kernel, grid, dim3(kWG), 0, q->stream, m1->seq, ix1, m2->seq, m2->data_indices + lo, n,
+                       q->min_ov, q->max_mm, ins ? ins + lo : nullptr, pos1 ? pos1 + lo : nullptr,
                        pos2 ? pos2 + lo : nullptr, q->d_scal);
-    HPGQ_HIP_TRY(hipGetLastError());
-  }
-  return HPGQ_OK;
+  });
 }
 
 }  // namespace
@@ -214,17 +200,9 @@ int hpgq_ovl_open(hpgq_ovl_t **ov, int device, int min_overlap, int max_mismatch
   int rc = hpgq::accum::use_device(device);
   if (rc) return rc;
   hpgq_ovl *q = new hpgq_ovl;
-  q->device = device;
   q->min_ov = min_overlap;
   q->max_mm = max_mismatches;
-  rc = q->stream.open(stream);
-  if (rc == HPGQ_OK && (hipMalloc(reinterpret_cast<void **>(&q->d_scal), kScalars * 8) != hipSuccess ||
-                        hipHostMalloc(reinterpret_cast<void **>(&q->h_scal), kScalars * 8 + 8, hipHostMallocDefault) != hipSuccess))
-    rc = HPGQ_E_NOMEM;
-  if (rc == HPGQ_OK && (hipMemsetAsync(q->d_scal, 0, kScalars * 8, q->stream) != hipSuccess ||
-                        hipDeviceGetAttribute(&q->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess))
-    rc = HPGQ_E_HIP;
-  if (rc) {
+  if ((rc = q->open(device, stream, kScalars)) != HPGQ_OK) {
     hpgq_ovl_close(q);
     return rc;
   }
@@ -234,17 +212,11 @@ int hpgq_ovl_open(hpgq_ovl_t **ov, int device, int min_overlap, int max_mismatch
 
 void hpgq_ovl_close(hpgq_ovl_t *q) {
   if (!q) return;
-  (void)hipSetDevice(q->device);
-  if (q->stream) (void)hipStreamSynchronize(q->stream);
-  q->retired.free_all();
-  (void)hipFree(q->d_scal);
-  q->scan.free();
+  q->close();
   for (int m = 0; m < 2; ++m) {
     q->pos[m].free();
     q->kept[m].free();
   }
-  if (q->h_scal) (void)hipHostFree(q->h_scal);
-  q->stream.close();
   delete q;
 }
 
@@ -264,15 +236,14 @@ int hpgq_ovl_batch_device(hpgq_ovl_t *q, const hpgq_batch_t *m1, const hpgq_batc
   const hpgq_batch_t b[2] = {*m1, *m2};   // (an input and an output may be the same struct)
   hpgq_batch_t *const out[2] = {out1, out2};
   const int64_t n = b[0].num_reads;
-  const hpgq::cut::Ctx c = q->ctx();
   for (int m = 0; m < 2; ++m) {
-    int rc = q->kept[m].reserve(c, b[m], reinterpret_cast<int32_t *>(q->h_scal + kScalars));
-    if (rc == HPGQ_OK && n) rc = q->pos[m].need(c, n);
+    int rc = q->kept[m].reserve(*q, b[m]);
+    if (rc == HPGQ_OK && n) rc = q->pos[m].need(*q, n);
     if (rc) return rc;
   }
   int rc = n ? find(q, &b[0], &b[1], nullptr, q->pos[0].d, q->pos[1].d) : HPGQ_OK;
   for (int m = 0; m < 2 && rc == HPGQ_OK; ++m)
-    rc = hpgq::cut::scan_and_copy(c, q->scan, &b[m], q->pos[m].d, q->kept[m].o_seq, q->kept[m].o_qual, q->kept[m].o_idx);
+    rc = hpgq::cut::scan_and_copy(*q, &b[m], q->pos[m].d, q->kept[m].o_seq, q->kept[m].o_qual, q->kept[m].o_idx);
   if (rc) return rc;
   for (int m = 0; m < 2; ++m) q->kept[m].give(out[m], n);
   return HPGQ_OK;
@@ -280,12 +251,7 @@ int hpgq_ovl_batch_device(hpgq_ovl_t *q, const hpgq_batch_t *m1, const hpgq_batc
 
 int hpgq_ovl_sync(hpgq_ovl_t *q) { return q ? q->settle() : HPGQ_E_INVALID; }
 
-int hpgq_ovl_reset(hpgq_ovl_t *q) {
-  if (!q) return HPGQ_E_INVALID;
-  HPGQ_HIP_TRY(hipSetDevice(q->device));
-  HPGQ_HIP_TRY(hipMemsetAsync(q->d_scal, 0, kScalars * 8, q->stream));
-  return HPGQ_OK;
-}
+int hpgq_ovl_reset(hpgq_ovl_t *q) { return q ? q->reset() : HPGQ_E_INVALID; }
 
 int hpgq_ovl_read(hpgq_ovl_t *q, hpgq_ovl_info_t *info) {
   if (!q || !info) return HPGQ_E_INVALID;
@@ -303,9 +269,7 @@ int hpgq_ovl_read(hpgq_ovl_t *q, hpgq_ovl_info_t *info) {
 }
 
 int hpgq_ovl_debug_set_max_workgroups(hpgq_ovl_t *q, int max_wg) {
-  if (!q || max_wg < 0) return HPGQ_E_INVALID;
-  q->max_wg = max_wg;
-  return HPGQ_OK;
+  return q ? q->set_max_workgroups(max_wg) : HPGQ_E_INVALID;
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // hpgq_reads.h — how a wave gets at the reads of a step (device side of the
-// per-read statistics: hpgq_qdist.hip, hpgq_adapt.hip, hpgq_dup.hip and the
-// descriptors of hpgq_kmers.hip).  Everything here is inlined
+// per-read kernels: hpgq_qdist.hip, hpgq_adapt.hip, hpgq_dup.hip, hpgq_clip.hip,
+// hpgq_ovl.hip, hpgq_cut.h and the descriptors of hpgq_kmers.hip).  Everything here is inlined
 // and wave-uniform but the lane's own offset, so the descriptors stay in SGPRs.
 //
 // What is readable.  A batch is n reads back to back in `bytes` (seq or
@@ -76,9 +76,41 @@ __device__ __forceinline__ v2u lane_load8(const __amdgpu_buffer_rsrc_t bytes, ui
   return __builtin_amdgcn_raw_buffer_load_b64(bytes, need ? (st & ~3u) + 4u * (uint32_t)lane : kNone, 0, 0);
 }
 
+// A step's R reads one after the other, PRE of their first loads (lane_load8
+// of the read's first 256 bytes) in flight; ix: step_reads' offsets.
+// scanned(i, len): read i of len bytes is looked at (otherwise its load moves
+// nothing); each(i, a, len, w): read i at a of `bytes`, w its first load.
+// Both are wave-uniform but w.
+template <int R, int PRE, class Scanned, class Each>
+__device__ __forceinline__ void walk_reads(const Batch &b, int32_t ix, int lane, Scanned scanned, Each each) {
+  static_assert(R % PRE == 0, "the reads of a wave step go in blocks of PRE");
+  auto first_load = [&](int i) {
+    const int32_t a = __builtin_amdgcn_readlane(ix, i);
+    const int32_t len = __builtin_amdgcn_readlane(ix, i + 1) - a;
+    return lane_load8(b.bytes, (uint32_t)a + b.shift, scanned(i, len) ? len : 0, lane);
+  };
+  v2u wq[PRE];
+#pragma unroll
+  for (int j = 0; j < PRE; ++j) wq[j] = first_load(j);
+  for (int i0 = 0; i0 < R; i0 += PRE) {
+#pragma unroll
+    for (int j = 0; j < PRE; ++j) {
+      const int i = i0 + j;
+      const int32_t a = __builtin_amdgcn_readlane(ix, i);
+      const int32_t len = __builtin_amdgcn_readlane(ix, i + 1) - a;
+      const v2u w = wq[j];
+      if (i0 + PRE < R) wq[j] = first_load(i + PRE);
+      each(i, a, len, w);
+    }
+  }
+}
+
 // The lane's four bytes v (those past the read's end zeroed) as four 2-bit
 // codes c (base j at bits 2j .. 2j + 1) and four validity bits ok (base j at bit
-// j): the byte is exactly the one base with its code.
+// j): the byte is exactly the one base with its code.  The four bytes at once:
+// x the code of each byte ((b >> 1) & 3: A 0, C 1, T 2, G 3), d its difference
+// from the one byte with that code that is a base (0x41 + 2 code, and T = 0x54
+// for code 2), z bit 7 of every byte where d is 0 (the zero-byte test).
 __device__ __forceinline__ void pack4(uint32_t v, uint32_t &c, uint32_t &ok) {
   const uint32_t x = v >> 1 & 0x03030303u;
   const uint32_t isT = x >> 1 & ~x & 0x01010101u;

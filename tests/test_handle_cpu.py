@@ -38,6 +38,8 @@ HANDLES = [
     ("hpgq_kmers", lambda: E.Kmers(150)),
     ("hpgq_qdist", lambda: E.QualityDist(150)),
     ("hpgq_adapt", lambda: E.AdapterContent([b"ACGTACGTAC"])),
+    ("hpgq_clip", lambda: E.AdapterClip([b"ACGTACGTAC"])),
+    ("hpgq_ovl", lambda: E.OverlapClip()),
     ("hpgq_dup", lambda: E.Duplication()),
     ("hpgq_gs", lambda: E.Signature(4)),
     ("hpgq_parser", lambda: E.Parser()),
@@ -76,7 +78,8 @@ def test_del_after_a_constructor_that_raised_calls_nothing(monkeypatch, prefix, 
 
 
 def test_del_of_an_object_whose_init_never_ran_calls_nothing(stub):
-    for cls in (E.Engine, E.Kmers, E.QualityDist, E.AdapterContent, E.Duplication, E.Signature, E.Parser, E.ChaosGame):
+    for cls in (E.Engine, E.Kmers, E.QualityDist, E.AdapterContent, E.AdapterClip, E.OverlapClip, E.Duplication, E.Signature,
+                E.Parser, E.ChaosGame):
         h = cls.__new__(cls)
         h.close()
         h.__del__()
