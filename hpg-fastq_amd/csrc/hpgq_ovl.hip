@@ -7,6 +7,11 @@
 //                      keeps, and the six scalars.  It reads both mates'
 //                      sequence bytes and offsets.
 //   scan and copy      hpgq_cut.h, once per mate: the kept reads back to back.
+//   ovl_fix_kernel     (--correct-overlap, §2.14) the facing bases of the kept
+//                      reads that disagree, the better quality's copied over
+//                      the worse, in place in the handle's kept buffers.
+//   ovl_hist_kernel    (--insert-size, §2.14) the F* of a part into the
+//                      handle's histogram.
 //
 // What the handle owns beyond its own state (stream, scalars, replaced buffers,
 // grid limits, the scan's storage) is hpgq_cut.h's Cutter, shared with
@@ -40,6 +45,9 @@ constexpr int kWaves = kWG / 64;
 constexpr int kR = 16;                // pairs per wave step
 constexpr int kGroup = kWaves * kR;   // pairs per workgroup step
 constexpr int kScalars = 6;           // pairs, skipped, overlapping, clipped, bases_removed[2]
+constexpr int kFixScalars = 3;        // behind them: corrected_pairs, corrected_bases[2]
+constexpr int kBins = HPGQ_OVL_INSERT_BINS;
+static_assert(2 * kMaxLen - 8 < kBins, "every F* has a bin");
 using reads::v2u;
 static_assert(kMaxLen == HPGQ_OVL_MAX_LEN, "the packed pair holds the longest analysed mate");
 static_assert(kMaxLen == 2 * 4 * 64, "two steps of 4 bytes per lane cover a mate");
@@ -158,14 +166,149 @@ __global__ void __launch_bounds__(kWG) ovl_find_kernel(const char *seq1, const i
   }
 }
 
+// the byte that faces b in a match, 0 if b is no base
+__device__ __forceinline__ uint32_t comp_of(uint32_t b) {
+  return b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : 0u;
+}
+
+// The four bytes at at .. at + 3 of a descriptor (at >= -3, any alignment) in
+// the opposite order: byte t of the result is the byte at at + 3 - t.  The two
+// dwords that hold them; the one below offset 0 is not loaded, its bytes are 0.
+__device__ __forceinline__ uint32_t load4_backwards(const __amdgpu_buffer_rsrc_t rq, int32_t at, bool need) {
+  const int32_t al = at & ~3;   // (two's complement: -3 .. -1 -> -4)
+  const uint32_t w0 = __builtin_amdgcn_raw_buffer_load_b32(rq, need && al >= 0 ? (uint32_t)al : reads::kNone, 0, 0);
+  const uint32_t w1 = __builtin_amdgcn_raw_buffer_load_b32(rq, need ? (uint32_t)(al + 4) : reads::kNone, 0, 0);
+  return __builtin_bswap32(__builtin_amdgcn_alignbyte(w1, w0, (uint32_t)at & 3u));
+}
+
+// §2.14's correction on the kept reads of a part, in place.  seq1 .. idx2: the
+// handle's kept batches (idx: the part's n + 1 offsets), ins: the part's F*.
+// Read-major like the find: a wave takes kR pairs one after the other, a pair
+// with F* <= 0 costs nothing more.  With lo = F - c2 and hi = c1 (the kept
+// lengths: §2.14), lane l of step s holds k = 256 s + 4 l .. + 3 of mate 1 (one
+// dword of sequence, one of quality) and the four bytes of mate 2 that face
+// them, j = F - 1 - k down to F - 4 - k: contiguous, backwards.  Positions
+// outside [lo, hi) are masked.  A byte is stored only where a rule fires, as a
+// byte, by the one lane that holds its position; no dword is ever written.
+__global__ void __launch_bounds__(kWG) ovl_fix_kernel(char *seq1, char *qual1, const int32_t *idx1, char *seq2, char *qual2,
+                                                      const int32_t *idx2, const int32_t *ins, int64_t n, int phred, int high,
+                                                      int low, unsigned long long *scal) {
+  __shared__ unsigned long long red[kFixScalars * kWaves];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const reads::Batch s1 = reads::open<false>(seq1, idx1, n, nullptr);
+  const reads::Batch q1 = reads::open<false>(qual1, idx1, n, nullptr);
+  const reads::Batch s2 = reads::open<false>(seq2, idx2, n, nullptr);
+  const reads::Batch q2 = reads::open<false>(qual2, idx2, n, nullptr);
+  const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void *)ins, (short)0, (uint32_t)(n * 4), 0x00020000);
+  const int64_t ngroups = (n + kGroup - 1) / kGroup;
+  uint32_t cnt[kFixScalars] = {0, 0, 0};   // over this wave's pairs (wave-uniform)
+  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const int64_t rb = g * kGroup + wave * kR;
+    if (rb >= n) continue;
+    int32_t ix1, ix2;
+    uint32_t mk, mk2;
+    reads::step_reads<kR, false>(s1, rb, n, lane, ix1, mk);
+    reads::step_reads<kR, false>(s2, rb, n, lane, ix2, mk2);
+    const int32_t fv = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(
+        rf, rb + lane < n && lane < kR ? (uint32_t)(rb + lane) * 4u : reads::kNone, 0, 0);
+    for (int i = 0; i < kR; ++i) {
+      if ((uint32_t)__builtin_amdgcn_readlane((int)mk, i) != 1u) break;   // past the batch (wave-uniform)
+      const int F = __builtin_amdgcn_readlane(fv, i);
+      if (F <= 0) continue;
+      const int32_t a1 = __builtin_amdgcn_readlane(ix1, i), a2 = __builtin_amdgcn_readlane(ix2, i);
+      const int c1 = __builtin_amdgcn_readlane(ix1, i + 1) - a1, c2 = __builtin_amdgcn_readlane(ix2, i + 1) - a2;
+      const int lo = F - c2, hi = min(c1, kMaxLen);
+      if (lo < 0 || hi > F || lo >= hi) continue;   // (not what the find and the cut leave: nothing is touched)
+      uint32_t fixed1 = 0, fixed2 = 0;   // the lane's corrected bases of this pair
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int k0 = 256 * s;
+        if (k0 >= hi || k0 + 256 <= lo) continue;   // (wave-uniform)
+        const int k = k0 + 4 * lane;
+        const bool mine = k + 3 >= lo && k < hi;
+        const int rem = mine ? hi - k0 : 0;
+        const uint32_t st1 = (uint32_t)a1 + s1.shift + (uint32_t)k0, sq1 = (uint32_t)a1 + q1.shift + (uint32_t)k0;
+        const uint32_t b1 = reads::lane_bytes(reads::lane_load8(s1.bytes, st1, rem, lane), st1, rem, lane);
+        const uint32_t p1 = reads::lane_bytes(reads::lane_load8(q1.bytes, sq1, rem, lane), sq1, rem, lane);
+        const int j3 = F - 4 - k;   // the lowest of the four facing positions: -3 at least where the lane is `mine`
+        const uint32_t b2 = load4_backwards(s2.bytes, a2 + (int32_t)s2.shift + j3, mine);
+        const uint32_t p2 = load4_backwards(q2.bytes, a2 + (int32_t)q2.shift + j3, mine);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          const int kt = k + t;
+          const uint32_t x1 = b1 >> (8 * t) & 255u, x2 = b2 >> (8 * t) & 255u;
+          const uint32_t y1 = p1 >> (8 * t) & 255u, y2 = p2 >> (8 * t) & 255u;
+          const uint32_t m1 = comp_of(x1), m2 = comp_of(x2);
+          const bool open = mine && kt >= lo && kt < hi && !(m1 != 0u && x2 == m1);
+          const int v1 = (int)y1 - phred, v2 = (int)y2 - phred;
+          const bool to2 = open && m1 != 0u && v1 >= high && v2 <= low;
+          const bool to1 = open && !to2 && m2 != 0u && v2 >= high && v1 <= low;
+          if (to2) {
+            const int64_t at = (int64_t)a2 + (F - 1 - kt);
+            reinterpret_cast<uint8_t *>(seq2)[at] = (uint8_t)m1;
+            reinterpret_cast<uint8_t *>(qual2)[at] = (uint8_t)y1;
+            ++fixed2;
+          }
+          if (to1) {
+            const int64_t at = (int64_t)a1 + kt;
+            reinterpret_cast<uint8_t *>(seq1)[at] = (uint8_t)m2;
+            reinterpret_cast<uint8_t *>(qual1)[at] = (uint8_t)y2;
+            ++fixed1;
+          }
+        }
+      }
+      if (__ballot((fixed1 | fixed2) != 0u) == 0ull) continue;
+      ++cnt[0];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {   // (a lane corrects 0 .. 8 bases per mate)
+        cnt[1] += (uint32_t)__popcll(__ballot((fixed1 >> b & 1u) != 0u)) << b;
+        cnt[2] += (uint32_t)__popcll(__ballot((fixed2 >> b & 1u) != 0u)) << b;
+      }
+    }
+  }
+  if (lane == 0)
+    for (int k = 0; k < kFixScalars; ++k) red[k * kWaves + wave] = cnt[k];
+  __syncthreads();
+  if (threadIdx.x < kFixScalars) {
+    unsigned long long s = 0;
+    for (int w2 = 0; w2 < kWaves; ++w2) s += red[threadIdx.x * kWaves + w2];
+    if (s) atomicAdd(&scal[kScalars + threadIdx.x], s);
+  }
+}
+
+// hist[F*] += 1 over a part's pairs, -1 (skipped) in no bin: a table per
+// workgroup in LDS, then one u64 atomic per cell that counted (a workgroup
+// sees at most a part's 2^28 pairs: the u32 cells hold them).
+__global__ void __launch_bounds__(kWG) ovl_hist_kernel(const int32_t *ins, int64_t n, unsigned long long *hist) {
+  __shared__ uint32_t table[kBins];
+  for (int c = threadIdx.x; c < kBins; c += kWG) table[c] = 0;
+  __syncthreads();
+  for (int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x; i < n; i += (int64_t)gridDim.x * kWG) {
+    const int32_t f = ins[i];
+    if ((uint32_t)f < (uint32_t)kBins) atomicAdd(&table[f], 1u);
+  }
+  __syncthreads();
+  for (int c = threadIdx.x; c < kBins; c += kWG) {
+    const uint32_t v = table[c];
+    if (v) atomicAdd(&hist[c], (unsigned long long)v);
+  }
+}
+
 }  // namespace ovl
 }  // namespace hpgq
 
-// the scalars: [pairs, skipped, overlapping, clipped, bases_removed[2]]
+// the scalars: [pairs, skipped, overlapping, clipped, bases_removed[2], corrected_pairs, corrected_bases[2]]
 struct hpgq_ovl : hpgq::cut::Cutter {
   int min_ov = 0, max_mm = 0;
   hpgq::cut::Positions pos[2];              // hpgq_ovl_batch_device's positions, per mate
   hpgq::cut::Kept kept[2];                  // and its outputs
+  // §2.14, nothing of it allocated while both switches are off
+  bool fix_on = false, hist_on = false;
+  int phred = HPGQ_PHRED33, high = 30, low = 14;
+  hpgq::cut::Positions ins;                 // F* (int32) where the caller keeps none
+  const int32_t *last_ins = nullptr;        // hpgq_ovl_batch_device's, while a switch was on (hpgq_ovl_last_inserts)
+  unsigned long long *d_hist = nullptr;     // [HPGQ_OVL_INSERT_BINS]
 };
 
 namespace {
@@ -177,8 +320,15 @@ bool pair_ok(const hpgq_batch_t *m1, const hpgq_batch_t *m2) {
   return batch_ok(m1) && batch_ok(m2) && m1->num_reads == m2->num_reads;
 }
 
-// the find pass over the pairs, async; every output may be null
+// the find pass over the pairs, async; every output may be null.  While the
+// inserts are counted, F* goes to the handle's own buffer where the caller
+// keeps none, and every part's into the histogram.
 int find(hpgq_ovl *q, const hpgq_batch_t *m1, const hpgq_batch_t *m2, int32_t *ins, uint32_t *pos1, uint32_t *pos2) {
+  if (!ins && q->hist_on) {
+    const int rc = q->ins.need(*q, m1->num_reads);
+    if (rc) return rc;
+    ins = reinterpret_cast<int32_t *>(q->ins.d);
+  }
   return hpgq::accum::for_parts(m1, nullptr, [&](const int32_t *ix1, const uint8_t *, int64_t n) {
     const int64_t lo = ix1 - m1->data_indices;
     // four workgroups of 512 threads per CU stay resident (5.5 KB of LDS each)
@@ -186,6 +336,23 @@ int find(hpgq_ovl *q, const hpgq_batch_t *m1, const hpgq_batch_t *m2, int32_t *i
     hipLaunchKernelGGL(ovl_find_kernel, grid, dim3(kWG), 0, q->stream, m1->seq, ix1, m2->seq, m2->data_indices + lo, n,
                        q->min_ov, q->max_mm, ins ? ins + lo : nullptr, pos1 ? pos1 + lo : nullptr,
                        pos2 ? pos2 + lo : nullptr, q->d_scal);
+    if (q->hist_on)
+      hipLaunchKernelGGL(ovl_hist_kernel, dim3(q->grid(4, (n + kWG - 1) / kWG)), dim3(kWG), 0, q->stream, ins + lo, n,
+                         q->d_hist);
+  });
+}
+
+// §2.14's correction of the kept batches, async: after both copies
+int fix(hpgq_ovl *q, int64_t n) {
+  hpgq_batch_t k1;
+  q->kept[0].give(&k1, n);
+  const hpgq::cut::Kept &o1 = q->kept[0], &o2 = q->kept[1];
+  return hpgq::accum::for_parts(&k1, nullptr, [&](const int32_t *ix1, const uint8_t *, int64_t np) {
+    const int64_t lo = ix1 - o1.o_idx;
+    const dim3 grid(q->grid(4, (np + kGroup - 1) / kGroup));
+    hipLaunchKernelGGL(ovl_fix_kernel, grid, dim3(kWG), 0, q->stream, o1.o_seq, o1.o_qual, ix1, o2.o_seq, o2.o_qual,
+                       o2.o_idx + lo, reinterpret_cast<const int32_t *>(q->ins.d) + lo, np, q->phred, q->high, q->low,
+                       q->d_scal);
   });
 }
 
@@ -202,7 +369,7 @@ int hpgq_ovl_open(hpgq_ovl_t **ov, int device, int min_overlap, int max_mismatch
   hpgq_ovl *q = new hpgq_ovl;
   q->min_ov = min_overlap;
   q->max_mm = max_mismatches;
-  if ((rc = q->open(device, stream, kScalars)) != HPGQ_OK) {
+  if ((rc = q->open(device, stream, kScalars + kFixScalars)) != HPGQ_OK) {
     hpgq_ovl_close(q);
     return rc;
   }
@@ -217,6 +384,8 @@ void hpgq_ovl_close(hpgq_ovl_t *q) {
     q->pos[m].free();
     q->kept[m].free();
   }
+  q->ins.free();
+  (void)hipFree(q->d_hist);
   delete q;
 }
 
@@ -225,6 +394,7 @@ int hpgq_ovl_find_device(hpgq_ovl_t *q, const hpgq_batch_t *m1, const hpgq_batch
   if (!q || !pair_ok(m1, m2)) return HPGQ_E_INVALID;
   if (m1->num_reads == 0) return HPGQ_OK;
   HPGQ_HIP_TRY(hipSetDevice(q->device));
+  q->last_ins = nullptr;
   return find(q, m1, m2, insert_out, pos1_out, pos2_out);
 }
 
@@ -241,17 +411,84 @@ int hpgq_ovl_batch_device(hpgq_ovl_t *q, const hpgq_batch_t *m1, const hpgq_batc
     if (rc == HPGQ_OK && n) rc = q->pos[m].need(*q, n);
     if (rc) return rc;
   }
-  int rc = n ? find(q, &b[0], &b[1], nullptr, q->pos[0].d, q->pos[1].d) : HPGQ_OK;
+  const bool fixes = q->fix_on && n;
+  int rc = fixes ? q->ins.need(*q, n) : HPGQ_OK;
+  if (rc) return rc;
+  if (n) rc = find(q, &b[0], &b[1], fixes ? reinterpret_cast<int32_t *>(q->ins.d) : nullptr, q->pos[0].d, q->pos[1].d);
   for (int m = 0; m < 2 && rc == HPGQ_OK; ++m)
     rc = hpgq::cut::scan_and_copy(*q, &b[m], q->pos[m].d, q->kept[m].o_seq, q->kept[m].o_qual, q->kept[m].o_idx);
+  if (rc == HPGQ_OK && fixes) rc = fix(q, n);
   if (rc) return rc;
+  q->last_ins = n && (q->fix_on || q->hist_on) ? reinterpret_cast<const int32_t *>(q->ins.d) : nullptr;
   for (int m = 0; m < 2; ++m) q->kept[m].give(out[m], n);
   return HPGQ_OK;
 }
 
 int hpgq_ovl_sync(hpgq_ovl_t *q) { return q ? q->settle() : HPGQ_E_INVALID; }
 
-int hpgq_ovl_reset(hpgq_ovl_t *q) { return q ? q->reset() : HPGQ_E_INVALID; }
+int hpgq_ovl_reset(hpgq_ovl_t *q) {
+  if (!q) return HPGQ_E_INVALID;
+  const int rc = q->reset();
+  if (rc) return rc;
+  if (q->d_hist) HPGQ_HIP_TRY(hipMemsetAsync(q->d_hist, 0, sizeof(uint64_t) * kBins, q->stream));
+  return HPGQ_OK;
+}
+
+int hpgq_ovl_set_correct(hpgq_ovl_t *q, int on, int phred, int high, int low) {
+  if (!q) return HPGQ_E_INVALID;
+  if (on) {
+    uint32_t none[2];
+    if (hpgq_ovl_correct(nullptr, nullptr, 0, nullptr, nullptr, 0, 0, phred, high, low, none) == -2) return HPGQ_E_INVALID;   // the rules of §2.14
+    q->phred = phred;
+    q->high = high;
+    q->low = low;
+  }
+  q->fix_on = on != 0;
+  return HPGQ_OK;
+}
+
+int hpgq_ovl_count_inserts(hpgq_ovl_t *q, int on) {
+  if (!q) return HPGQ_E_INVALID;
+  if (on && !q->d_hist) {
+    HPGQ_HIP_TRY(hipSetDevice(q->device));
+    if (hipMalloc(&q->d_hist, sizeof(uint64_t) * kBins) != hipSuccess) return HPGQ_E_NOMEM;
+    HPGQ_HIP_TRY(hipMemsetAsync(q->d_hist, 0, sizeof(uint64_t) * kBins, q->stream));
+  }
+  q->hist_on = on != 0;
+  return HPGQ_OK;
+}
+
+int hpgq_ovl_last_inserts(hpgq_ovl_t *q, const int32_t **inserts) {
+  if (!q || !inserts) return HPGQ_E_INVALID;
+  *inserts = q->last_ins;
+  return HPGQ_OK;
+}
+
+int hpgq_ovl_read_correct(hpgq_ovl_t *q, hpgq_ovl_correct_info_t *info) {
+  if (!q || !info) return HPGQ_E_INVALID;
+  const int rc = q->settle();
+  if (rc) return rc;
+  info->corrected_pairs = q->h_scal[kScalars];
+  info->corrected_bases[0] = q->h_scal[kScalars + 1];
+  info->corrected_bases[1] = q->h_scal[kScalars + 2];
+  info->on = q->fix_on;
+  info->phred = q->phred;
+  info->high = q->high;
+  info->low = q->low;
+  return HPGQ_OK;
+}
+
+int hpgq_ovl_read_inserts(hpgq_ovl_t *q, uint64_t hist[HPGQ_OVL_INSERT_BINS]) {
+  if (!q || !hist) return HPGQ_E_INVALID;
+  const int rc = q->settle();
+  if (rc) return rc;
+  if (!q->d_hist) {
+    std::fill(hist, hist + kBins, (uint64_t)0);
+    return HPGQ_OK;
+  }
+  HPGQ_HIP_TRY(hipMemcpy(hist, q->d_hist, sizeof(uint64_t) * kBins, hipMemcpyDeviceToHost));
+  return HPGQ_OK;
+}
 
 int hpgq_ovl_read(hpgq_ovl_t *q, hpgq_ovl_info_t *info) {
   if (!q || !info) return HPGQ_E_INVALID;

@@ -1,5 +1,5 @@
 // hpgq_ovl_post.cpp — host side of `edit --clip-overlap`: the
-// overlap rule on one pair.  HIP-free, no device.
+// overlap rule on one pair, and §2.14's correction of one pair.  HIP-free, no device.
 //
 // For a candidate insert length F, s1[k] faces s2[F - 1 - k] for k in
 // [max(0, F - n2), min(n1, F)).  F is admissible iff that range holds at least
@@ -43,4 +43,41 @@ extern "C" int64_t hpgq_ovl_find(const void *s1, size_t n1, const void *s2, size
     if (mism <= max_mismatches) return F;
   }
   return 0;
+}
+
+// §2.14: at the facing positions of insert length F that do not match, the
+// base of high quality over the one of low quality, quality byte with it.
+extern "C" int64_t hpgq_ovl_correct(void *s1, void *q1, size_t n1, void *s2, void *q2, size_t n2, int64_t F, int phred,
+                                    int high, int low, uint32_t changed[2]) {
+  if (phred < 0 || phred > 255 || low < 0 || low >= high || high > 93 || ((!s1 || !q1) && n1) || ((!s2 || !q2) && n2))
+    return -2;
+  if (changed) changed[0] = changed[1] = 0;
+  if (F <= 0) return 0;
+  if (n1 > HPGQ_OVL_MAX_LEN || n2 > HPGQ_OVL_MAX_LEN) return -2;
+  const int64_t N1 = (int64_t)n1, N2 = (int64_t)n2;
+  const int64_t lo = F > N2 ? F - N2 : 0, hi = N1 < F ? N1 : F;
+  if (hi - lo < 8) return -2;   // (no min_overlap admits this F)
+  unsigned char *a = static_cast<unsigned char *>(s1), *b = static_cast<unsigned char *>(s2);
+  unsigned char *qa = static_cast<unsigned char *>(q1), *qb = static_cast<unsigned char *>(q2);
+  uint32_t done[2] = {0, 0};
+  for (int64_t k = lo; k < hi; ++k) {
+    const int64_t j = F - 1 - k;
+    const unsigned char ca = comp(a[k]), cb = comp(b[j]);
+    if (ca && b[j] == ca) continue;
+    const int v1 = (int)qa[k] - phred, v2 = (int)qb[j] - phred;
+    if (ca && v1 >= high && v2 <= low) {
+      b[j] = ca;
+      qb[j] = qa[k];
+      ++done[1];
+    } else if (cb && v2 >= high && v1 <= low) {
+      a[k] = cb;
+      qa[k] = qb[j];
+      ++done[0];
+    }
+  }
+  if (changed) {
+    changed[0] = done[0];
+    changed[1] = done[1];
+  }
+  return (int64_t)done[0] + done[1];
 }

@@ -155,6 +155,9 @@ int main(int argc, char **argv) {
   }
   /* --clip-overlap: one file for the pairs, named as mate 1's report set would be */
   if (r.ovl_on && cli_report_ovl(o, &r.ovl, mate_name[0])) rc = 1;
+  /* --correct-overlap and --insert-size: one file each, beside it */
+  if (r.ovl_fix_on && cli_report_ovl_correct(o, &r.ovl, &r.ovl_fix, mate_name[0])) rc = 1;
+  if (r.ovl_insert_on && cli_report_insert(o, &r.ovl, r.ovl_inserts, mate_name[0])) rc = 1;
 
   if (!o->quiet) {
     printf("\n\nRESULTS\n");
@@ -174,6 +177,7 @@ int main(int argc, char **argv) {
       const char *ok = cmd == CMD_FILTER ? "passed" : "edit";
       if (cmd == CMD_EDIT) printf("Num. edited reads : %lu (mate 1)\n", (unsigned long)r.num_edited);
       if (r.ovl_on) printf("Num. overlap-clipped pairs : %lu\n", (unsigned long)r.ovl.clipped);
+      if (r.ovl_fix_on) printf("Num. overlap-corrected pairs : %lu\n", (unsigned long)r.ovl_fix.corrected_pairs);
       if (r.clip_on) printf("Num. clipped reads : %lu (mate 1)\n", (unsigned long)r.clip[0].clipped);
       printf("Num. passed pairs : %lu (%s/%s_1.fq, %s/%s_2.fq)\n", (unsigned long)r.num_passed, o->out_dirname, ok,
              o->out_dirname, ok);

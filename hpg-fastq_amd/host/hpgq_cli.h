@@ -51,6 +51,10 @@ typedef struct {
   int ovl_on;               /* edit --clip-overlap: paired input only */
   int ovl_min_overlap;      /* --clip-overlap-min: 8 .. HPGQ_OVL_MAX_LEN */
   int ovl_max_mismatches;   /* --clip-overlap-mismatches: 0 .. 255, below the minimum overlap */
+  int ovl_fix_on;           /* --correct-overlap: needs --clip-overlap */
+  int ovl_fix_high;         /* --correct-overlap-high: 1 .. 93 */
+  int ovl_fix_low;          /* --correct-overlap-low: 0 .. 92, below the high quality */
+  int ovl_insert_on;        /* --insert-size (§2.14): needs --clip-overlap */
   /* chaos game (old/main_hpg_fastq_old.c:185-189: --cg | --chaos-game, --k, --gs-filename) */
   int cg_on, k_cg;
   char *gs_filename;
@@ -123,6 +127,10 @@ typedef struct {
   hpgq_clip_info_t clip[2];
   int ovl_on;               /* --clip-overlap: ovl holds the pairs' scalars, the workers' added */
   hpgq_ovl_info_t ovl;
+  int ovl_fix_on;           /* --correct-overlap: ovl_fix holds the correction's scalars, the workers' added */
+  hpgq_ovl_correct_info_t ovl_fix;
+  int ovl_insert_on;        /* --insert-size: ovl_inserts holds the histogram, the workers' added */
+  uint64_t ovl_inserts[HPGQ_OVL_INSERT_BINS];
   uint32_t *cg_seq, *cg_q;  /* --cg: table_seq / table_q [dim*dim] (malloc'd) */
   uint32_t cg_words;        /* fq_word_count */
   int cg_exact_calls;       /* chaos-game calls the exact simulation redid */
@@ -163,6 +171,12 @@ int cli_report_clip(const cli_options_t *o, int nprobes, const char *const *name
                     const char *base);
 /* --clip-overlap: <base>.overlap.clip.data from the pairs' scalars (base: mate 1's report base) */
 int cli_report_ovl(const cli_options_t *o, const hpgq_ovl_info_t *info, const char *base);
+/* --correct-overlap: <base>.overlap.correct.data from the pairs' and the correction's scalars */
+int cli_report_ovl_correct(const cli_options_t *o, const hpgq_ovl_info_t *info, const hpgq_ovl_correct_info_t *fix,
+                           const char *base);
+/* --insert-size: <base>.insert.size.data from the pairs' scalars and the histogram */
+int cli_report_insert(const cli_options_t *o, const hpgq_ovl_info_t *info, const uint64_t hist[HPGQ_OVL_INSERT_BINS],
+                      const char *base);
 const char *cli_base_name(const char *path);
 /* the report base names of the two mates: each input's base name, or
  * <base>_1 / <base>_2 for --interleaved (out: 2 x 4096 bytes) */

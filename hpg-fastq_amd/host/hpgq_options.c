@@ -11,7 +11,8 @@
  *  and --duplication / --duplication-out
  * (§2.9), --adapters / --adapter-file / --adapters-out (§2.11), --clip-adapters /
  * --clip-adapter-file / --clip-min-overlap (§2.12), --clip-overlap /
- * --clip-overlap-min / --clip-overlap-mismatches (§2.13).
+ * --clip-overlap-min / --clip-overlap-mismatches (§2.13), --correct-overlap /
+ * --correct-overlap-high / --correct-overlap-low / --insert-size (§2.14).
  * --quality-encoding is accepted by every command
  * (quirk Q11).
  */
@@ -71,7 +72,7 @@ int cli_parse_range(int *min, int *max, const char *range, const char *msg) {
   return 1;
 }
 
-static void usage(const cli_options_t *o) {
+static void usage_status(const cli_options_t *o, int status) {
   printf("Usage: %s %s [options]   (%s)\n\n", o->exec_name, o->command_name,
          kCommandHelp[o->command]);
   printf("  -h, --help                      Help option\n");
@@ -105,6 +106,10 @@ static void usage(const cli_options_t *o) {
     printf("  --clip-overlap                  Paired input: cut both mates where the sequenced fragment ends, found from the mates' overlap\n");
     printf("  --clip-overlap-min=<int>        Bases the mates must overlap by (8-%d, default 30)\n", HPGQ_OVL_MAX_LEN);
     printf("  --clip-overlap-mismatches=<int> Overlap positions that may differ (0-255, below the minimum overlap; default 5)\n");
+    printf("  --correct-overlap               With --clip-overlap: where the mates disagree, the base of high quality replaces the one of low quality\n");
+    printf("  --correct-overlap-high=<int>    Quality from which a base wins (1-93, default 30)\n");
+    printf("  --correct-overlap-low=<int>     Quality up to which a base loses (0-92, below the high quality; default 14)\n");
+    printf("  --insert-size                   With --clip-overlap: the histogram of the insert sizes found\n");
   }
   printf("  --read-length-range=<string>    Read length range, eg. 80,110\n");
   printf("  --read-quality-range=<string>   Read quality range, eg. 20,40\n");
@@ -141,8 +146,10 @@ static void usage(const cli_options_t *o) {
            "  --copy-threads=<int>            Mapped writer: copier threads (default --num-threads)\n"
            "  --prefault-threads=<int>        Mapped writer: threads populating the outputs ahead (default 0)\n");
   printf("  --quiet                         No parameter / result display\n");
-  exit(-1);
+  exit(status);
 }
+
+static void usage(const cli_options_t *o) { usage_status(o, -1); }
 
 static int exists(const char *path) {
   struct stat st;
@@ -167,7 +174,8 @@ enum {
   O_RQRANGE, O_MAXN, O_MAXOOQ, O_GPU, O_LMAX, O_CHUNK, O_PRINT, O_COUNTERS, O_QUIET,
   O_KMERSOUT, O_CG, O_KCG, O_GS, O_GPUS, O_CGBATCH, O_CGOUT, O_GPUW, O_STREAMW, O_WHOOK, O_COPYT, O_PFT,
   O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT, O_DUP, O_DUPOUT, O_OVER, O_OVERMIN, O_OVERTOP, O_OVERBYTES,
-  O_ADAPT, O_ADAPTFILE, O_ADAPTOUT, O_CLIP, O_CLIPFILE, O_CLIPOV, O_OVL, O_OVLMIN, O_OVLMM
+  O_ADAPT, O_ADAPTFILE, O_ADAPTOUT, O_CLIP, O_CLIPFILE, O_CLIPOV, O_OVL, O_OVLMIN, O_OVLMM,
+  O_FIX, O_FIXHIGH, O_FIXLOW, O_INSERT
 };
 
 /* a whole-string decimal in [lo, hi] (u64), else the usage error */
@@ -211,6 +219,9 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   int ovl_values = 0;       /* --clip-overlap-min or --clip-overlap-mismatches was given */
   o->ovl_min_overlap = 30;
   o->ovl_max_mismatches = 5;
+  int fix_values = 0;       /* --correct-overlap-high or --correct-overlap-low was given */
+  o->ovl_fix_high = 30;
+  o->ovl_fix_low = 14;
   static const struct option longopts[] = {
       {"help", no_argument, 0, 'h'},
       {"fastq-file", required_argument, 0, 'f'},
@@ -263,6 +274,10 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
       {"clip-overlap", no_argument, 0, O_OVL},
       {"clip-overlap-min", required_argument, 0, O_OVLMIN},
       {"clip-overlap-mismatches", required_argument, 0, O_OVLMM},
+      {"correct-overlap", no_argument, 0, O_FIX},
+      {"correct-overlap-high", required_argument, 0, O_FIXHIGH},
+      {"correct-overlap-low", required_argument, 0, O_FIXLOW},
+      {"insert-size", no_argument, 0, O_INSERT},
       {"quiet", no_argument, 0, O_QUIET},
       {"stream-writer", no_argument, 0, O_STREAMW},
       {"writer-test-hook", required_argument, 0, O_WHOOK},
@@ -365,6 +380,20 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
         if (c == O_OVLMIN) o->ovl_min_overlap = count_arg(o, "clip-overlap-min", optarg, 8, HPGQ_OVL_MAX_LEN);
         if (c == O_OVLMM) o->ovl_max_mismatches = count_arg(o, "clip-overlap-mismatches", optarg, 0, 255);
         break;
+      case O_FIX:
+      case O_FIXHIGH:
+      case O_FIXLOW:
+      case O_INSERT:
+        if (command != CMD_EDIT) {   /* one line, before anything is opened or written */
+          fprintf(stderr, "hpg-fastq: --%s is an option of the edit command, not of %s\n",
+                  c == O_INSERT ? "insert-size" : "correct-overlap", o->command_name);
+          exit(1);
+        }
+        if (c == O_FIX) o->ovl_fix_on = 1;
+        if (c == O_INSERT) o->ovl_insert_on = 1;
+        if (c == O_FIXHIGH) o->ovl_fix_high = count_arg(o, "correct-overlap-high", optarg, 1, 93), fix_values = 1;
+        if (c == O_FIXLOW) o->ovl_fix_low = count_arg(o, "correct-overlap-low", optarg, 0, 92), fix_values = 1;
+        break;
       case O_CG:
         if (command != CMD_STATS) usage(o);
         o->cg_on = 1;
@@ -436,6 +465,18 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
     printf("\nError: --clip-overlap-mismatches (%d) must be below --clip-overlap-min (%d)\n", o->ovl_max_mismatches,
            o->ovl_min_overlap);
     usage(o);
+  }
+  if ((o->ovl_fix_on || fix_values || o->ovl_insert_on) && !o->ovl_on) {
+    printf("\nError: --correct-overlap, --correct-overlap-high, --correct-overlap-low and --insert-size need --clip-overlap\n");
+    usage_status(o, 1);
+  }
+  if (fix_values && !o->ovl_fix_on) {
+    printf("\nError: --correct-overlap-high and --correct-overlap-low need --correct-overlap\n");
+    usage_status(o, 1);
+  }
+  if (o->ovl_fix_on && o->ovl_fix_low >= o->ovl_fix_high) {
+    printf("\nError: --correct-overlap-low (%d) must be below --correct-overlap-high (%d)\n", o->ovl_fix_low, o->ovl_fix_high);
+    usage_status(o, 1);
   }
   if (fq1) o->in_filename = fq1;
   o->paired = o->in_filename2 != NULL || o->interleaved;
@@ -564,6 +605,9 @@ void cli_display(const cli_options_t *o) {
   if (o->ovl_on)
     printf("\tOverlap clipping     : min overlap %d, max mismatches %d (--clip-overlap)\n", o->ovl_min_overlap,
            o->ovl_max_mismatches);
+  if (o->ovl_fix_on)
+    printf("\tOverlap correction   : high quality %d, low quality %d (--correct-overlap)\n", o->ovl_fix_high, o->ovl_fix_low);
+  if (o->ovl_insert_on) printf("\tInsert sizes         : counted (--insert-size)\n");
   if (o->clip_on)
     printf("\tAdapter clipping     : %d probes, min overlap %d (--clip-adapters)\n", o->adapter_n, o->clip_min_overlap);
   printf("\n%s options\n", o->command == CMD_EDIT ? "Edit and filter" : "Filter");

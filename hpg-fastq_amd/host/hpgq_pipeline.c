@@ -815,6 +815,8 @@ typedef struct {
   hpgq_adapt_t *ad[2];    /* --adapters: one table per mate, on the ctx stream */
   hpgq_clip_t *cl[2];     /* --clip-adapters: one handle per mate, on the ctx stream */
   hpgq_ovl_t *ov;         /* --clip-overlap: one handle for the pair, on the ctx stream */
+  int32_t *h_ins;         /* --correct-overlap: the unit's F* on the host ([ins_cap]), for correct_text */
+  size_t ins_cap;
   hpgq_cgr_t *cg;
   uint8_t *d_mask;
   uint32_t *d_trim;
@@ -846,6 +848,10 @@ static int worker_open(worker_t *W) {
   /* --clip-overlap cuts both mates of a pair before anything else sees them */
   if (rc == 0 && o->ovl_on)
     rc = hpgq_ovl_open(&W->ov, W->device, o->ovl_min_overlap, o->ovl_max_mismatches, hpgq_stream(W->ctx));
+  /* --correct-overlap and --insert-size are switches of that handle (§2.14) */
+  if (rc == 0 && o->ovl_fix_on)
+    rc = hpgq_ovl_set_correct(W->ov, 1, o->quality_encoding_value, o->ovl_fix_high, o->ovl_fix_low);
+  if (rc == 0 && o->ovl_insert_on) rc = hpgq_ovl_count_inserts(W->ov, 1);
   /* --clip-adapters cuts each mate on its own before the engine sees it */
   for (int m = 0; m < W->P->nmates && rc == 0 && o->clip_on; ++m) {
     const char *probes[HPGQ_ADAPT_MAX_PROBES];
@@ -882,6 +888,7 @@ static void worker_close(worker_t *W) {
   hpgq_clip_close(W->cl[0]);
   hpgq_clip_close(W->cl[1]);
   hpgq_ovl_close(W->ov);
+  free(W->h_ins);
   hpgq_dup_close(W->dp[0]);
   hpgq_dup_close(W->dp[1]);
   hpgq_cgr_close(W->cg);
@@ -932,6 +939,34 @@ static void record_name(const char *buf, size_t use, int64_t r, char *out, size_
     out[k++] = c;
   }
   out[k] = 0;
+}
+
+/* --correct-overlap: the writers assemble the outputs from
+ * the unit's text, not from the device's kept reads, so the correction the
+ * device made for the stages behind it is made here once more, by the same
+ * rule on the host (hpgq_ovl_correct), in place in the text: pair i with
+ * ins[i] = F* > 0, each mate's sequence and quality line.  The lengths are the
+ * records' own (a "\r\n" line end is not part of them). */
+static int correct_text(const pipe_t *P, slot_t *s, const int32_t *ins) {
+  const cli_options_t *o = P->o;
+  const mate_view_t v[2] = {mate_view(P, s, 0), mate_view(P, s, 1)};
+  for (int64_t i = 0; i < s->nreads; ++i) {
+    if (ins[i] <= 0) continue;
+    char *seq[2], *qual[2];
+    size_t len[2];
+    for (int m = 0; m < 2; ++m) {
+      const int64_t r = v[m].first + i * v[m].stride;
+      char *buf = (char *)v[m].buf;   /* (the slot's own, writable text) */
+      seq[m] = buf + v[m].ss[r];
+      qual[m] = buf + v[m].qs[r];
+      len[m] = v[m].ps[r] - v[m].ss[r] - 1;
+      if (len[m] && seq[m][len[m] - 1] == '\r') --len[m];
+    }
+    if (hpgq_ovl_correct(seq[0], qual[0], len[0], seq[1], qual[1], len[1], ins[i], o->quality_encoding_value,
+                         o->ovl_fix_high, o->ovl_fix_low, NULL) < 0)
+      return HPGQ_E_INVALID;
+  }
+  return HPGQ_OK;
 }
 
 /* One chunk on the worker's GPU: its nm mates parsed (one text, two texts, or
@@ -1020,10 +1055,23 @@ static int worker_chunk(worker_t *W, slot_t *s) {
     for (int m = 0; m < ns && rc == 0; ++m)
       rc = hpgq_parse_records(W->ps[m], s->rec_start + m * n, s->seq_start + m * n, s->plus_start + m * n,
                               s->qual_start + m * n);
+    /* --correct-overlap: the unit's F* for correct_text */
+    if (rc == 0 && W->ov && o->ovl_fix_on) {
+      const int32_t *d_ins = NULL;
+      rc = hpgq_ovl_last_inserts(W->ov, &d_ins);
+      if (rc == 0 && n > W->ins_cap) {
+        free(W->h_ins);
+        W->ins_cap = n + n / 4 + 1024;
+        W->h_ins = malloc(W->ins_cap * sizeof(int32_t));
+        if (!W->h_ins) W->ins_cap = 0, rc = HPGQ_E_NOMEM;
+      }
+      if (rc == 0) rc = hpgq_copy_to_host(W->ctx, W->h_ins, d_ins, n * sizeof(int32_t));
+    }
   }
   trace_at(P, s->chunk, 3, -1);
   if (rc == 0) rc = hpgq_sync(W->ctx);
   trace_at(P, s->chunk, 6, -1);
+  if (rc == 0 && writes && W->ov && o->ovl_fix_on) rc = correct_text(P, s, W->h_ins);
   if (rc == 0 && edit && !P->mmap_out) rc = assemble_edit(P, s);
   if (rc == 0 && W->cg) {   /* after the parse and the mask; settled before the next parse reuses b */
     rc = hpgq_cgr_fill_device(W->cg, &b[0], o->filter_on ? W->d_mask : NULL,
@@ -1315,6 +1363,27 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
     res->ovl.bases_removed[1] += info.bases_removed[1];
     res->ovl.min_overlap = info.min_overlap;
     res->ovl.max_mismatches = info.max_mismatches;
+  }
+  /* --correct-overlap, --insert-size: the workers' scalars and histograms added */
+  for (int w = 0; w < G && rc == 0 && o->ovl_fix_on; ++w) {
+    hpgq_ovl_correct_info_t fix;
+    res->ovl_fix_on = 1;
+    rc = hpgq_ovl_read_correct(W[w].ov, &fix);
+    if (rc) break;
+    res->ovl_fix.corrected_pairs += fix.corrected_pairs;
+    res->ovl_fix.corrected_bases[0] += fix.corrected_bases[0];
+    res->ovl_fix.corrected_bases[1] += fix.corrected_bases[1];
+    res->ovl_fix.on = fix.on;
+    res->ovl_fix.phred = fix.phred;
+    res->ovl_fix.high = fix.high;
+    res->ovl_fix.low = fix.low;
+  }
+  for (int w = 0; w < G && rc == 0 && o->ovl_insert_on; ++w) {
+    uint64_t *hist = malloc(sizeof(uint64_t) * HPGQ_OVL_INSERT_BINS);
+    res->ovl_insert_on = 1;
+    rc = hist ? hpgq_ovl_read_inserts(W[w].ov, hist) : HPGQ_E_NOMEM;
+    for (int f = 0; f < HPGQ_OVL_INSERT_BINS && rc == 0; ++f) res->ovl_inserts[f] += hist[f];
+    free(hist);
   }
   /* --adapters: per mate, the workers' tables added at the longest worker's
    * positions (hpgq_adapt_add), and the two scalars added */

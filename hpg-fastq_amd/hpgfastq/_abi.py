@@ -35,6 +35,7 @@ QDIST_VALUES = 256
 DUP_LEVELS = 16
 ADAPT_MAX_PROBES, ADAPT_MIN_LEN, ADAPT_MAX_LEN = 32, 8, 32
 OVL_MAX_LEN = 512
+OVL_INSERT_BINS = 1025
 
 
 class HpgqError(RuntimeError):
@@ -109,6 +110,11 @@ class ClipInfo(C.Structure):
 class OvlInfo(C.Structure):
     _fields_ = [("pairs", C.c_uint64), ("skipped", C.c_uint64), ("overlapping", C.c_uint64), ("clipped", C.c_uint64),
                 ("bases_removed", C.c_uint64 * 2), ("min_overlap", C.c_int32), ("max_mismatches", C.c_int32)]
+
+
+class OvlCorrectInfo(C.Structure):
+    _fields_ = [("corrected_pairs", C.c_uint64), ("corrected_bases", C.c_uint64 * 2), ("on", C.c_int32),
+                ("phred", C.c_int32), ("high", C.c_int32), ("low", C.c_int32)]
 
 
 class GsInfo(C.Structure):
@@ -266,6 +272,13 @@ _SIGS = [
     ("hpgq_ovl_read", C.c_int, [C.c_void_p, C.POINTER(OvlInfo)]),
     ("hpgq_ovl_debug_set_max_workgroups", C.c_int, [C.c_void_p, C.c_int]),
     ("hpgq_ovl_find", C.c_int64, [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int, C.c_int]),
+    ("hpgq_ovl_set_correct", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    ("hpgq_ovl_count_inserts", C.c_int, [C.c_void_p, C.c_int]),
+    ("hpgq_ovl_read_correct", C.c_int, [C.c_void_p, C.POINTER(OvlCorrectInfo)]),
+    ("hpgq_ovl_read_inserts", C.c_int, [C.c_void_p, C.c_void_p]),
+    ("hpgq_ovl_last_inserts", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("hpgq_ovl_correct", C.c_int64, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
+                                     C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     ("hpgq_synth_length", C.c_int32, [C.POINTER(Synth), C.c_int64]),
     ("hpgq_synth_indices_host", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p]),
     ("hpgq_synth_device", C.c_int, [C.POINTER(Synth), C.c_int64, C.c_int64, C.c_void_p,

@@ -9,7 +9,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, AdaptInfo, ClipInfo, OvlInfo, counters_len,
+from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, AdaptInfo, ClipInfo, OvlInfo, OvlCorrectInfo, OVL_INSERT_BINS,
+                   counters_len,
                    CGR_ALL_READS, ROUTES, E_PAIRING, QDIST_VALUES, DUP_LEVELS, HpgqError)
 
 # Kernel route for new Engines (tests / A/B: a key of ROUTES, or None for the
@@ -518,13 +519,53 @@ class OverlapClip(_Handle):
     """hpgq_ovl: `edit --clip-overlap`, a pair's insert length from the overlap of
     mate 1 with the reverse complement of mate 2 (at least `min_overlap` facing
     bases, at most `max_mismatches` of them not complementary), both mates cut
-    there.  All pointers are device pointers (ints)."""
+    there.  `correct`: (phred, high, low) switches on the
+    correction of the kept reads' facing bases, `inserts` the histogram of the
+    insert lengths (§2.14); both are off by default and can be switched between
+    any two calls.  All pointers are device pointers (ints)."""
 
     _prefix = "hpgq_ovl"
 
-    def __init__(self, min_overlap=30, max_mismatches=5, device=0, stream=None):
+    def __init__(self, min_overlap=30, max_mismatches=5, correct=None, inserts=False, device=0, stream=None):
         self.min_overlap, self.max_mismatches = int(min_overlap), int(max_mismatches)
         self._open(device, self.min_overlap, self.max_mismatches, stream)
+        if correct is not None:
+            self.set_correct(correct)
+        if inserts:
+            self.count_inserts(True)
+
+    def set_correct(self, correct):
+        """hpgq_ovl_set_correct: clip_batch corrects from now on with correct =
+        (phred, high, low); None: it does not."""
+        if correct is None:
+            self._call("set_correct", 0, 0, 0, 0)
+        else:
+            phred, high, low = correct
+            self._call("set_correct", 1, int(phred), int(high), int(low))
+
+    def count_inserts(self, on=True):
+        """hpgq_ovl_count_inserts: every find and clip_batch counts its F* from now on (or no longer)."""
+        self._call("count_inserts", int(bool(on)))
+
+    def correct_info(self):
+        """dict(corrected_pairs, corrected_bases [2], on, phred, high, low); synchronises."""
+        i = OvlCorrectInfo()
+        self._call("read_correct", C.byref(i))
+        return dict(corrected_pairs=int(i.corrected_pairs), corrected_bases=[int(x) for x in i.corrected_bases],
+                    on=bool(i.on), phred=int(i.phred), high=int(i.high), low=int(i.low))
+
+    def last_inserts_ptr(self):
+        """hpgq_ovl_last_inserts: the device pointer (int) to the F* (int32 [n]) of the last
+        clip_batch while a switch was on, None otherwise; valid until the next call."""
+        p = C.c_void_p()
+        self._call("last_inserts", C.byref(p))
+        return p.value
+
+    def inserts(self):
+        """hpgq_ovl_read_inserts: u64 [1025], pairs per F* (bin 0: analysed, no overlap); synchronises."""
+        out = np.zeros(OVL_INSERT_BINS, dtype=np.uint64)
+        self._call("read_inserts", _ptr(out))
+        return out
 
     def find(self, mate1, mate2, insert_ptr=None, pos1_ptr=None, pos2_ptr=None):
         """hpgq_ovl_find_device: insert int32 [n], pos1 / pos2 u32 [n], each unless None (async)."""
@@ -554,6 +595,23 @@ def ovl_find(s1, s2, min_overlap=30, max_mismatches=5):
     if f == -2:
         raise HpgqError(-1, "hpgq_ovl_find")
     return int(f)
+
+
+def ovl_correct(s1, q1, s2, q2, F, phred=33, high=30, low=14):
+    """hpgq_ovl_correct: §2.14's correction of one pair whose F* is F.  Returns
+    (s1, q1, s2, q2, [bases changed in mate 1, in mate 2]), the four as new bytes
+    (HpgqError -1 for parameters that break the rules or an F the pair cannot have)."""
+    bufs = [C.create_string_buffer(bytes(x), max(len(x), 1)) for x in (s1, q1, s2, q2)]
+    if len(s1) != len(q1) or len(s2) != len(q2):
+        raise ValueError("a mate's quality is as long as its sequence")
+    changed = (C.c_uint32 * 2)()
+    r = lib.hpgq_ovl_correct(bufs[0], bufs[1], len(s1), bufs[2], bufs[3], len(s2), int(F), int(phred), int(high), int(low),
+                             changed)
+    if r == -2:
+        raise HpgqError(-1, "hpgq_ovl_correct")
+    out = [b.raw[:len(x)] for b, x in zip(bufs, (s1, q1, s2, q2))]
+    assert r == changed[0] + changed[1]
+    return (*out, [int(changed[0]), int(changed[1])])
 
 
 def _levels_dict(lv):

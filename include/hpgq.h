@@ -889,6 +889,62 @@ int  hpgq_ovl_debug_set_max_workgroups(hpgq_ovl_t *ov, int max_wg);
 int64_t hpgq_ovl_find(const void *s1, size_t n1, const void *s2, size_t n2, int min_overlap,
                       int max_mismatches);
 
+/*
+ * edit --correct-overlap and --insert-size (build-defined).
+ * Both are switches of an ovl handle, off after hpgq_ovl_open; while both are
+ * off the handle allocates and launches nothing for them.
+ *
+ * Correction.  Q1, Q2 are the mates' quality bytes (unsigned, 0 .. 255), phred
+ * is 0 .. 255 as for hpgq_open, 0 <= low < high <= 93.  With F = F* > 0 and k
+ * in [lo, hi), j = F - 1 - k, q1 = (int)Q1[k] - phred, q2 = (int)Q2[j] - phred:
+ * at a position that does not match (the rule above),
+ *   1. if s1[k] is one of A C G T, q1 >= high and q2 <= low:
+ *      s2[j] := comp(s1[k]), Q2[j] := Q1[k]  (one corrected base of mate 2);
+ *   2. else if s2[j] is one of A C G T, q2 >= high and q1 <= low:
+ *      s1[k] := comp(s2[j]), Q1[k] := Q2[j]  (one corrected base of mate 1);
+ *   3. else nothing.
+ * F*, the cuts and the scalars of hpgq_ovl_info_t come from the uncorrected
+ * bytes; every facing position lies inside the kept reads, which are what
+ * hpgq_ovl_batch_device corrects, after the cut, in the handle's buffers.  The
+ * inputs are never written, hpgq_ovl_find_device never corrects.
+ *
+ * Insert sizes.  hist[F*] counts every analysed pair of every find pass
+ * (hpgq_ovl_find_device and hpgq_ovl_batch_device) while counting is on: bin 0
+ * the pairs without an admissible F, skipped pairs in no bin.
+ */
+#define HPGQ_OVL_INSERT_BINS 1025   /* F* <= 2 HPGQ_OVL_MAX_LEN - 8 */
+typedef struct hpgq_ovl_correct_info {
+  uint64_t corrected_pairs, corrected_bases[2];   /* pairs with a corrected base; bases per mate */
+  int32_t on, phred, high, low;
+} hpgq_ovl_correct_info_t;
+/* on != 0: hpgq_ovl_batch_device corrects from now on, with these parameters
+ * (HPGQ_E_INVALID for ones that break the rules, before any device call);
+ * on == 0: it does not, and the parameters given are ignored.  Between any two
+ * calls on the handle. */
+int  hpgq_ovl_set_correct(hpgq_ovl_t *ov, int on, int phred, int high, int low);
+/* on != 0: every find pass counts its F* from now on */
+int  hpgq_ovl_count_inserts(hpgq_ovl_t *ov, int on);
+/* the correction's scalars since open or reset (hpgq_ovl_reset zeroes them and
+ * the histogram; the switches and parameters stay).  Synchronises. */
+int  hpgq_ovl_read_correct(hpgq_ovl_t *ov, hpgq_ovl_correct_info_t *info);
+/* the histogram since open or reset, all zeros if counting was never on.  Synchronises. */
+int  hpgq_ovl_read_inserts(hpgq_ovl_t *ov, uint64_t hist[HPGQ_OVL_INSERT_BINS]);
+/* *inserts: the DEVICE array of the F* (int32, num_reads of them) that the last
+ * hpgq_ovl_batch_device found, kept while either switch was on during that
+ * call; NULL otherwise, and after hpgq_ovl_find_device.  Valid until the next
+ * call on the handle; written on its stream.  For a consumer that assembles its
+ * output from text of its own: with these and hpgq_ovl_correct it applies the
+ * same correction there. */
+int  hpgq_ovl_last_inserts(hpgq_ovl_t *ov, const int32_t **inserts);
+/* Host only, no device (csrc/hpgq_ovl_post.cpp): the correction above, in
+ * place, on one pair whose F* is F.  Returns the bases changed and sets
+ * changed[0] / changed[1] (may be NULL) to those of mate 1 / mate 2; 0 and
+ * nothing changed for F <= 0; -2 for parameters that break the rules, a NULL
+ * array with bytes, or an F > 0 that the rule above cannot return for these
+ * lengths (a mate longer than HPGQ_OVL_MAX_LEN, fewer than 8 facing bytes). */
+int64_t hpgq_ovl_correct(void *s1, void *q1, size_t n1, void *s2, void *q2, size_t n2, int64_t F,
+                         int phred, int high, int low, uint32_t changed[2]);
+
 /* ---------------------------------------------------------------------- */
 /* FASTQ text -> device batch (the parsing half of the producer's          */
 /* fastq_fread_se, src/stats_fastq.c:183, moved onto the GPU)              */

@@ -15,7 +15,18 @@ passes (default probes, min overlap 8) together; ovl_vs_two_finds is the ratio o
 the medians.  Everything also goes to --out (default profiles/ovl_rate.json).  Not a
 test; fails without a GPU.
 
+--correct and --inserts switch on the handle's overlap correction (phred 33,
+thresholds 30 / 14) and its insert-size histogram for the
+ovl_batch timing; the filling "short" (only with --fillings) makes every pair
+from a fragment of 30 .. L - 1 bases and flips 1 % of mate 1's bases.  The
+qualities run through 33 .. 73 along the batch, so facing bases differ in
+quality.  --shapes / --fillings pick some of them, --only-batch times
+hpgq_ovl_batch_device alone: for A/B runs of one call, each variant a process of
+its own (HPGQ_LIB_PATH loads another build of the library).
+
     python tools/ovl_rate.py [--pairs 10000000] [--steps 20] [--warmup 5] [--out profiles/ovl_rate.json]
+                             [--correct] [--inserts] [--shapes 150bp,250bp] [--fillings none,overlap,readthrough,short]
+                             [--only-batch]
 """
 import argparse
 import json
@@ -46,6 +57,9 @@ def fill_pairs(torch, seq1, seq2, n, L, filling, gen):
             if filling == "overlap":
                 F = torch.randint(L + 1, 2 * L - 30 + 1, (m, 1), device="cuda", generator=gen)
                 on = torch.ones((m, 1), dtype=torch.bool, device="cuda")
+            elif filling == "short":
+                F = torch.randint(30, L, (m, 1), device="cuda", generator=gen)
+                on = torch.ones((m, 1), dtype=torch.bool, device="cuda")
             else:
                 F = torch.randint(30, L, (m, 1), device="cuda", generator=gen)
                 on = torch.rand((m, 1), device="cuda", generator=gen) < 0.2
@@ -54,6 +68,8 @@ def fill_pairs(torch, seq1, seq2, n, L, filling, gen):
             rc = comp[frag.gather(1, src)]
             b = torch.where(on & (col < F), rc, other)
             a = torch.where(on & (col >= F), other.flip(1), a)
+            if filling == "short":   # 1 % of mate 1's bases become another base
+                a = torch.where(torch.rand((m, L), device="cuda", generator=gen) < 0.01, (a + 1) % 4, a)
             made += int(on.sum().item())
         v1[lo:lo + m] = lut[a]
         v2[lo:lo + m] = lut[b]
@@ -77,6 +93,11 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ovl_rate.json"))
+    ap.add_argument("--correct", action="store_true", help="ovl_batch with the overlap correction on (33, 30, 14)")
+    ap.add_argument("--inserts", action="store_true", help="ovl_batch with the insert sizes counted")
+    ap.add_argument("--shapes", default="150bp,250bp")
+    ap.add_argument("--fillings", default="none,overlap,readthrough")
+    ap.add_argument("--only-batch", action="store_true", help="time hpgq_ovl_batch_device alone")
     a = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -92,17 +113,45 @@ def main():
     calls = a.warmup + a.steps
     rows = []
     for name, L in (("150bp", 150), ("250bp", 250)):
+        if name not in a.shapes.split(","):
+            continue
         n = min(a.pairs, (2 ** 31 - 1024) // L)   # data_indices are int32: < 2 GiB of bases per batch
         total = n * L
         idx = (torch.arange(n + 1, dtype=torch.int64, device="cuda") * L).to(torch.int32)
         seq = [torch.zeros(total + H.DEVICE_SLACK, dtype=torch.uint8, device="cuda") for _ in range(2)]
-        qual = torch.full((total + H.DEVICE_SLACK,), ord("I"), dtype=torch.uint8, device="cuda")
+        qual = (33 + torch.arange(total + H.DEVICE_SLACK, dtype=torch.int64, device="cuda") * 7 % 41).to(torch.uint8)
         ins = torch.empty(n, dtype=torch.int32, device="cuda")
         pos = [torch.empty(n, dtype=torch.int32, device="cuda") for _ in range(2)]
         b = [H.engine.device_batch(n, s.data_ptr(), qual.data_ptr(), idx.data_ptr()) for s in seq]
-        for filling in ("none", "overlap", "readthrough"):
+        for filling in a.fillings.split(","):
             made = fill_pairs(torch, seq[0], seq[1], n, L, filling, gen)
             torch.cuda.synchronize()
+            if a.only_batch:
+                with H.OverlapClip(30, 5, stream=sp) as ov:
+                    if a.correct:
+                        ov.set_correct((33, 30, 14))
+                    if a.inserts:
+                        ov.count_inserts(True)
+                    cut_us = timed(torch, stream, lambda: ov.clip_batch(b[0], b[1]), a.warmup, a.steps)
+                    info = ov.info()
+                    fixed = ov.correct_info() if a.correct else None
+                    counted = int(ov.inserts().sum()) if a.inserts else None
+                per = {k: (v // calls if isinstance(v, int) else [x // calls for x in v]) for k, v in info.items()
+                       if k not in ("min_overlap", "max_mismatches")}
+                assert per["pairs"] == n and (counted is None or counted == n * calls), (info, counted)
+                if filling == "short":
+                    assert per["overlapping"] > n - n // 100 and per["clipped"] == per["overlapping"], info
+                    assert fixed is None or min(fixed["corrected_bases"]) > 0, fixed
+                kept = total * 2 - sum(per["bases_removed"])
+                res = {"tool": "ovl_rate", "shape": name, "pairs": n, "read_length": L, "filling": filling, "correct": a.correct,
+                       "inserts": a.inserts, "lib": os.path.basename(os.path.dirname(H.LIB_PATH)) + "/" + os.path.basename(H.LIB_PATH),
+                       "per_call": per, "steps": a.steps, "warmup": a.warmup, **box,
+                       "corrected_per_call": None if fixed is None else
+                       {"pairs": fixed["corrected_pairs"] // calls, "bases": [x // calls for x in fixed["corrected_bases"]]},
+                       "ovl_batch": summary(cut_us, 2 * total + 24 * n + 4 * kept + 16 * n, n)}
+                print(json.dumps(res), flush=True)
+                rows.append(res)
+                continue
             with H.AdapterClip(None, 8, stream=sp) as cl:
                 def two_finds():
                     cl.find(b[0], pos[0].data_ptr(), None)
@@ -114,6 +163,10 @@ def main():
                                 a.warmup, a.steps)
                 info = ov.info()
                 ov.reset()
+                if a.correct:
+                    ov.set_correct((33, 30, 14))
+                if a.inserts:
+                    ov.count_inserts(True)
                 cut_us = timed(torch, stream, lambda: ov.clip_batch(b[0], b[1]), a.warmup, a.steps)
                 ov.sync()
             per = {k: (v // calls if isinstance(v, int) else [x // calls for x in v]) for k, v in info.items()
@@ -128,7 +181,7 @@ def main():
             kept = total * 2 - sum(per["bases_removed"])
             f, c = summary(find_us, 2 * total + 20 * n, n), summary(clip_us, 2 * total + 16 * n, n)
             res = {"tool": "ovl_rate", "shape": name, "pairs": n, "read_length": L, "bases": 2 * total, "min_overlap": 30,
-                   "max_mismatches": 5, "filling": filling, "fragment_pairs": made, "per_call": per, "steps": a.steps,
+                   "max_mismatches": 5, "filling": filling, "correct": a.correct, "inserts": a.inserts, "fragment_pairs": made, "per_call": per, "steps": a.steps,
                    "warmup": a.warmup, **box,
                    # find: both mates' bases and offsets in, 12 bytes per pair out
                    "ovl_find": f,
