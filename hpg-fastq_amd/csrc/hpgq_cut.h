@@ -157,21 +157,29 @@ struct Positions {
   void free() { (void)hipFree(d); }
 };
 
+// the scan's storage for the inclusive sums of a batch of num_reads, part by part
+inline int scan_room(Cutter &c, int64_t num_reads) {
+  Scan &s = c.scan;
+  const int first = (int)std::min<int64_t>(num_reads, accum::kPart);
+  size_t tb = 0;
+  HPGQ_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, static_cast<const int32_t *>(nullptr),
+                                                static_cast<int32_t *>(nullptr), first, c.stream));
+  if (tb > s.tmp_bytes) {
+    const int rc = grow(c, &s.d_tmp, 1, tb, false);
+    if (rc) return rc;
+    s.tmp_bytes = tb;
+  }
+  return HPGQ_OK;
+}
+
 // idx_out[0] = 0, idx_out[i + 1] = idx_out[i] + pos[i], then the copy; async
 inline int scan_and_copy(Cutter &c, const hpgq_batch_t *b, const uint32_t *pos, char *seq_out, char *qual_out,
                          int32_t *idx_out) {
   Scan &s = c.scan;
   HPGQ_HIP_TRY(hipMemsetAsync(idx_out, 0, 4, c.stream));
   if (b->num_reads == 0) return HPGQ_OK;
-  const int first = (int)std::min<int64_t>(b->num_reads, accum::kPart);
-  size_t tb = 0;
-  HPGQ_HIP_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tb, reinterpret_cast<const int32_t *>(pos), idx_out + 1, first,
-                                                c.stream));
-  if (tb > s.tmp_bytes) {
-    const int rc = grow(c, &s.d_tmp, 1, tb, false);
-    if (rc) return rc;
-    s.tmp_bytes = tb;
-  }
+  const int rc = scan_room(c, b->num_reads);
+  if (rc) return rc;
   return accum::for_parts(b, nullptr, [&](const int32_t *ix, const uint8_t *, int64_t n) {
     const int64_t lo = ix - b->data_indices;
     size_t bytes = s.tmp_bytes;
@@ -196,15 +204,27 @@ struct Kept {
   // on the device: fetched through the handle's pinned extra word, one wait for
   // the stream) and its reads.
   int reserve(accum::Handle &c, const hpgq_batch_t &b) {
-    int32_t *const ends = static_cast<int32_t *>(c.h_extra());
     size_t bytes = 0;
+    const int rc = held(c, b, &bytes);
+    return rc ? rc : room(c, bytes, b.num_reads);
+  }
+
+  // the bytes b holds (one wait for the stream)
+  static int held(accum::Handle &c, const hpgq_batch_t &b, size_t *bytes) {
+    int32_t *const ends = static_cast<int32_t *>(c.h_extra());
+    *bytes = 0;
     if (b.num_reads) {
       HPGQ_HIP_TRY(hipMemcpyAsync(ends, b.data_indices, 4, hipMemcpyDeviceToHost, c.stream));
       HPGQ_HIP_TRY(hipMemcpyAsync(ends + 1, b.data_indices + b.num_reads, 4, hipMemcpyDeviceToHost, c.stream));
       HPGQ_HIP_TRY(hipStreamSynchronize(c.stream));
       if (ends[1] < ends[0]) return HPGQ_E_INVALID;
-      bytes = (size_t)(ends[1] - ends[0]);
+      *bytes = (size_t)(ends[1] - ends[0]);
     }
+    return HPGQ_OK;
+  }
+
+  // room for `bytes` bytes (and the slack) and `reads` reads
+  int room(accum::Handle &c, size_t bytes, int64_t reads) {
     if (!o_seq || bytes > o_bytes) {
       const size_t cap = std::max(bytes, o_bytes + o_bytes / 2);
       int rc = grow(c, &o_seq, 1, cap + HPGQ_DEVICE_SLACK, true);
@@ -212,8 +232,8 @@ struct Kept {
       if (rc) return rc;
       o_bytes = cap;
     }
-    if (b.num_reads > o_reads) {
-      const int64_t cap = std::max<int64_t>(b.num_reads, o_reads + o_reads / 2);
+    if (reads > o_reads) {
+      const int64_t cap = std::max<int64_t>(reads, o_reads + o_reads / 2);
       const int rc = grow(c, &o_idx, 4, (size_t)cap + 1, false);
       if (rc) return rc;
       o_reads = cap;

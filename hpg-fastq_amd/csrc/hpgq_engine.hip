@@ -64,6 +64,7 @@ constexpr int kProbeEvery = 16;   // wide-first calls between two hex-first prob
 struct hpgq_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
+  bool own_stream = true;   // (hpgq_open_on_stream: the caller's, never destroyed here)
   hpgq_params_t p{};
   int nm = 1;
   size_t clen = 0;
@@ -465,7 +466,16 @@ static int validate_params(const hpgq_params_t *p) {
 
 static size_t state_bytes(const hpgq_ctx *c) { return c->clen * c->nm * sizeof(uint64_t) + FL_WORDS * 4; }
 
-int hpgq_open(hpgq_ctx_t **out, int device, const hpgq_params_t *p) {
+static int open_ctx(hpgq_ctx_t **out, int device, const hpgq_params_t *p, hipStream_t callers);
+
+int hpgq_open(hpgq_ctx_t **out, int device, const hpgq_params_t *p) { return open_ctx(out, device, p, nullptr); }
+
+int hpgq_open_on_stream(hpgq_ctx_t **out, int device, const hpgq_params_t *p, void *stream) {
+  if (!stream) return HPGQ_E_INVALID;
+  return open_ctx(out, device, p, (hipStream_t)stream);
+}
+
+static int open_ctx(hpgq_ctx_t **out, int device, const hpgq_params_t *p, hipStream_t callers) {
   if (!out) return HPGQ_E_INVALID;
   *out = nullptr;
   int rc = validate_params(p);
@@ -483,7 +493,12 @@ int hpgq_open(hpgq_ctx_t **out, int device, const hpgq_params_t *p) {
   c->nm = p->paired ? 2 : 1;
   c->clen = hpgq_counters_len(p->lmax);
   HPGQ_HIP_TRY(hipSetDevice(device));
-  HPGQ_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  if (callers) {
+    c->stream = callers;
+    c->own_stream = false;
+  } else {
+    HPGQ_HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  }
   HPGQ_HIP_TRY(hipMalloc(&c->d_state, state_bytes(c)));
   c->d_flags = reinterpret_cast<uint32_t *>(c->d_state + c->clen * c->nm);
   HPGQ_HIP_TRY(hipMalloc(&c->d_global, c->clen * c->nm * sizeof(uint64_t)));
@@ -546,7 +561,7 @@ void hpgq_close(hpgq_ctx_t *c) {
   for (uint32_t *q : c->ovf_chunks) (void)hipFree(q);
   if (c->h_report) (void)hipHostFree(c->h_report);
   if (c->cstream) (void)hipStreamDestroy(c->cstream);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  if (c->stream && c->own_stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
 

@@ -12,6 +12,10 @@
 //                      the worse, in place in the handle's kept buffers.
 //   ovl_hist_kernel    (--insert-size, §2.14) the F* of a part into the
 //                      handle's histogram.
+//   ovl_plan_kernel, ovl_compact_kernel, ovl_merge_kernel
+//                      (--merge-overlap, §2.15, §4.18) the pairs with F* > 0 as
+//                      one read each in a third kept batch, the others uncut
+//                      in the two kept batches, all three compacted.
 //
 // What the handle owns beyond its own state (stream, scalars, replaced buffers,
 // grid limits, the scan's storage) is hpgq_cut.h's Cutter, shared with
@@ -46,6 +50,7 @@ constexpr int kR = 16;                // pairs per wave step
 constexpr int kGroup = kWaves * kR;   // pairs per workgroup step
 constexpr int kScalars = 6;           // pairs, skipped, overlapping, clipped, bases_removed[2]
 constexpr int kFixScalars = 3;        // behind them: corrected_pairs, corrected_bases[2]
+constexpr int kMergeScalars = 4;      // behind those: merged_pairs, merged_bases, resolved[2]
 constexpr int kBins = HPGQ_OVL_INSERT_BINS;
 static_assert(2 * kMaxLen - 8 < kBins, "every F* has a bin");
 using reads::v2u;
@@ -295,10 +300,163 @@ __global__ void __launch_bounds__(kWG) ovl_hist_kernel(const int32_t *ins, int64
   }
 }
 
+// §2.15's plan of a part: per pair the bytes each mate keeps as an unmerged
+// pair (everything, or nothing where the pair merges), the merged read's bytes
+// and the merged flag; mlen and flag are then summed in place.
+__global__ void __launch_bounds__(256) ovl_plan_kernel(const int32_t *idx1, const int32_t *idx2, const int32_t *ins, int64_t n,
+                                                       uint32_t *pos1, uint32_t *pos2, int32_t *mlen, int32_t *flag) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int32_t f = ins[i];
+    const bool merges = f > 0;
+    pos1[i] = merges ? 0u : (uint32_t)(idx1[i + 1] - idx1[i]);
+    pos2[i] = merges ? 0u : (uint32_t)(idx2[i + 1] - idx2[i]);
+    mlen[i] = merges ? f : 0;
+    flag[i] = merges ? 1 : 0;
+  }
+}
+
+// The three uncompacted offset arrays of a part (u1, u2, um: n + 1 offsets, a
+// pair that is not in an output has no bytes there) into the three compacted
+// data_indices, by rank: rank[i] counts the merged pairs up to and with pair i
+// of the whole batch, `first` is the part's first pair.  The part that ends the
+// batch (tail) writes the three totals behind the last entries.
+__global__ void __launch_bounds__(256) ovl_compact_kernel(const int32_t *u1, const int32_t *u2, const int32_t *um,
+                                                          const int32_t *rank, const int32_t *ins, int64_t n, int64_t first,
+                                                          int tail, int32_t *c1, int32_t *c2, int32_t *cm) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t r = rank[i];
+    const bool merges = ins[i] > 0;
+    if (merges) {
+      cm[r - 1] = um[i];
+    } else {
+      c1[first + i - r] = u1[i];
+      c2[first + i - r] = u2[i];
+    }
+    if (tail && i == n - 1) {
+      cm[r] = um[n];
+      c1[first + n - r] = u1[n];
+      c2[first + n - r] = u2[n];
+    }
+  }
+}
+
+// §2.15's merged reads of a part.  seq1 .. idx2: the inputs (idx: the part's
+// n + 1 offsets), ins: the part's F*, moff: the part's uncompacted merged
+// offsets (pair i's read at [moff[i], moff[i] + F*) of seq_out / qual_out,
+// which hipMalloc aligned).  Read-major like the fix: a wave takes kR pairs one
+// after the other, a pair with F* <= 0 costs nothing more.  In a step of 256
+// positions lane l holds p = 256 s + 4 l .. + 3: mate 1's dword of sequence and
+// of quality where p < hi, the four bytes of mate 2 that face them (backwards)
+// where p + 3 >= lo.  §2.15 on those four positions is merge4 (hpgq_ovl_lane.h):
+// dword arithmetic without a compare.  The lane's four merged bytes are then moved by the output
+// offset's residue (the lane below's dword; lane 0: lane 63's of the step
+// before) so that every lane holds one aligned output dword; it is stored as a
+// dword where it lies whole inside the read's range and byte by byte where it
+// does not: hpgq_cut.h's rule, no dword is read, modified and written.
+__global__ void __launch_bounds__(kWG) ovl_merge_kernel(const char *seq1, const char *qual1, const int32_t *idx1,
+                                                        const char *seq2, const char *qual2, const int32_t *idx2,
+                                                        const int32_t *ins, const int32_t *moff, int64_t n, char *seq_out,
+                                                        char *qual_out, unsigned long long *scal) {
+  __shared__ unsigned long long red[kMergeScalars];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const reads::Batch s1 = reads::open<false>(seq1, idx1, n, nullptr);
+  const reads::Batch q1 = reads::open<false>(qual1, idx1, n, nullptr);
+  const reads::Batch s2 = reads::open<false>(seq2, idx2, n, nullptr);
+  const reads::Batch q2 = reads::open<false>(qual2, idx2, n, nullptr);
+  const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void *)ins, (short)0, (uint32_t)(n * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)moff, (short)0, (uint32_t)(n * 4), 0x00020000);
+  const int nn = (int)n, ngroups = (nn + kGroup - 1) / kGroup;   // (a part: at most 2^28 pairs)
+  // over this wave's pairs, in the lanes' own registers: the pairs and their bases the same in every lane
+  // (lane 0's count), the resolved bases each lane's own
+  uint32_t pairs = 0, won1 = 0, won2 = 0;
+  unsigned long long bases = 0;
+  for (int g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const int rb = g * kGroup + wave * kR;
+    if (rb >= nn) continue;
+    int32_t ix1, ix2;
+    uint32_t mk, mk2;
+    reads::step_reads<kR, false>(s1, rb, n, lane, ix1, mk);
+    reads::step_reads<kR, false>(s2, rb, n, lane, ix2, mk2);
+    const uint32_t mine_at = rb + lane < nn && lane < kR ? (uint32_t)(rb + lane) * 4u : reads::kNone;
+    const int32_t fv = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(rf, mine_at, 0, 0);
+    const int32_t ov = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ro, mine_at, 0, 0);
+#pragma nounroll
+    for (int i = 0; i < kR; ++i) {
+      if ((uint32_t)__builtin_amdgcn_readlane((int)mk, i) != 1u) break;   // past the batch (wave-uniform)
+      const int F = __builtin_amdgcn_readlane(fv, i);
+      if (F <= 0) continue;
+      const int32_t a1 = __builtin_amdgcn_readlane(ix1, i), a2 = __builtin_amdgcn_readlane(ix2, i);
+      const int n1 = __builtin_amdgcn_readlane(ix1, i + 1) - a1, n2 = __builtin_amdgcn_readlane(ix2, i + 1) - a2;
+      const int32_t o = __builtin_amdgcn_readlane(ov, i);
+      const int lo = max(0, F - n2), hi = min(n1, F);
+      if ((uint32_t)n1 > (uint32_t)kMaxLen || (uint32_t)n2 > (uint32_t)kMaxLen || lo >= hi || o < 0)
+        continue;   // (not what the find and the plan leave: nothing is touched)
+      ++pairs;
+      bases += (unsigned long long)F;
+      const uint32_t sh = (uint32_t)o & 3u;
+      uint32_t last_s = 0, last_q = 0;   // the merged bytes of the step before (lane 63's are lane 0's lower dword)
+#pragma nounroll
+      for (int p0 = 0; p0 < F + (int)sh; p0 += 256) {   // (F <= 1016: four steps at most)
+        const int p = p0 + 4 * lane;
+        const int rem = hi - p0;         // mate 1's bytes from p0 on (none: nothing is loaded)
+        const uint32_t st1 = (uint32_t)a1 + s1.shift + (uint32_t)p0, sq1 = (uint32_t)a1 + q1.shift + (uint32_t)p0;
+        const uint32_t b1 = reads::lane_bytes(reads::lane_load8(s1.bytes, st1, rem, lane), st1, rem, lane);
+        const uint32_t p1 = reads::lane_bytes(reads::lane_load8(q1.bytes, sq1, rem, lane), sq1, rem, lane);
+        const bool faces = p + 3 >= lo && p < F;
+        const int j3 = F - 4 - p;        // the lowest of the four facing positions: -3 at least where the lane `faces`
+        const uint32_t b2 = load4_backwards(s2.bytes, a2 + (int32_t)s2.shift + j3, faces);
+        const uint32_t p2 = load4_backwards(q2.bytes, a2 + (int32_t)q2.shift + j3, faces);
+        const Merged4 m4 = merge4(b1, p1, b2, p2, hi - p, lo - p);
+        const uint32_t ms = m4.seq, mq = m4.qual;
+        won1 += m4.won1;
+        won2 += m4.won2;
+        // the aligned output dword at position pa: the last sh bytes of the lane below, the lane's first 4 - sh
+        const uint32_t us = (uint32_t)__builtin_amdgcn_ds_bpermute(((lane - 1) & 63) * 4, (int)(lane == 63 ? last_s : ms));
+        const uint32_t uq = (uint32_t)__builtin_amdgcn_ds_bpermute(((lane - 1) & 63) * 4, (int)(lane == 63 ? last_q : mq));
+        last_s = ms;
+        last_q = mq;
+        const uint32_t ds = sh ? __builtin_amdgcn_alignbyte(ms, us, 4u - sh) : ms;
+        const uint32_t dq = sh ? __builtin_amdgcn_alignbyte(mq, uq, 4u - sh) : mq;
+        const int pa = p - (int)sh;
+        char *const os = seq_out + ((int64_t)o + pa), *const oq = qual_out + ((int64_t)o + pa);
+        if (pa >= 0 && pa + 4 <= F) {
+          *reinterpret_cast<uint32_t *>(os) = ds;
+          *reinterpret_cast<uint32_t *>(oq) = dq;
+        } else {
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+            if ((uint32_t)(pa + t) < (uint32_t)F) {
+              reinterpret_cast<uint8_t *>(os)[t] = (uint8_t)(ds >> (8 * t));
+              reinterpret_cast<uint8_t *>(oq)[t] = (uint8_t)(dq >> (8 * t));
+            }
+        }
+      }
+    }
+  }
+  // the workgroup's four sums in LDS (u64: a lane's resolved bases stay below 2^32 in a part of 2^28 pairs of at
+  // most 12 facing positions per lane; the bases are summed as u64 from the start), then one u64 atomic per
+  // nonzero scalar
+  if (threadIdx.x < kMergeScalars) red[threadIdx.x] = 0;
+  __syncthreads();
+  if (lane == 0 && pairs) {
+    atomicAdd(&red[0], (unsigned long long)pairs);
+    atomicAdd(&red[1], bases);
+  }
+  if (won1) atomicAdd(&red[2], (unsigned long long)won1);
+  if (won2) atomicAdd(&red[3], (unsigned long long)won2);
+  __syncthreads();
+  if (threadIdx.x < kMergeScalars) {
+    const unsigned long long s = red[threadIdx.x];
+    if (s) atomicAdd(&scal[kScalars + kFixScalars + threadIdx.x], s);
+  }
+}
+
 }  // namespace ovl
 }  // namespace hpgq
 
-// the scalars: [pairs, skipped, overlapping, clipped, bases_removed[2], corrected_pairs, corrected_bases[2]]
+// the scalars: [pairs, skipped, overlapping, clipped, bases_removed[2], corrected_pairs, corrected_bases[2],
+// merged_pairs, merged_bases, resolved[2]]
 struct hpgq_ovl : hpgq::cut::Cutter {
   int min_ov = 0, max_mm = 0;
   hpgq::cut::Positions pos[2];              // hpgq_ovl_batch_device's positions, per mate
@@ -309,6 +467,10 @@ struct hpgq_ovl : hpgq::cut::Cutter {
   hpgq::cut::Positions ins;                 // F* (int32) where the caller keeps none
   const int32_t *last_ins = nullptr;        // hpgq_ovl_batch_device's, while a switch was on (hpgq_ovl_last_inserts)
   unsigned long long *d_hist = nullptr;     // [HPGQ_OVL_INSERT_BINS]
+  // §2.15, nothing of it allocated before the first hpgq_ovl_merge_device
+  hpgq::cut::Kept merged;                   // the merged reads
+  hpgq::cut::Positions uidx[2];             // the unmerged outputs' uncompacted offsets (int32 [n + 1])
+  hpgq::cut::Positions moff, rank;          // the merged reads' (int32 [n + 1]); the merged pairs up to each pair (int32 [n])
 };
 
 namespace {
@@ -356,6 +518,57 @@ int fix(hpgq_ovl *q, int64_t n) {
   });
 }
 
+// data[0, b's reads) into its inclusive sums, in place, async (the scan's storage: cut::scan_room)
+int sum_in_place(hpgq_ovl *q, const hpgq_batch_t *b, int32_t *data) {
+  int sum_rc = HPGQ_OK;
+  const int rc = hpgq::accum::for_parts(b, nullptr, [&](const int32_t *ix, const uint8_t *, int64_t n) {
+    const int64_t lo = ix - b->data_indices;
+    size_t bytes = q->scan.tmp_bytes;
+    if (hipcub::DeviceScan::InclusiveSum(q->scan.d_tmp, bytes, data + lo, data + lo, (int)n, q->stream) != hipSuccess)
+      sum_rc = HPGQ_E_HIP;
+    if (lo) hipLaunchKernelGGL(hpgq::cut::clip_carry_kernel, dim3(1024), dim3(256), 0, q->stream, data + lo, n, data + lo - 1);
+  });
+  return rc ? rc : sum_rc;
+}
+
+// §2.15 behind the find, async but for one wait: the plan, M, both unmerged
+// copies, the three compacted data_indices, the merged reads
+int merge(hpgq_ovl *q, const hpgq_batch_t b[2], int64_t *num_merged) {
+  const int64_t n = b[0].num_reads;
+  const int32_t *ins = reinterpret_cast<const int32_t *>(q->ins.d);
+  int32_t *const u1 = reinterpret_cast<int32_t *>(q->uidx[0].d), *const u2 = reinterpret_cast<int32_t *>(q->uidx[1].d);
+  int32_t *const um = reinterpret_cast<int32_t *>(q->moff.d), *const rank = reinterpret_cast<int32_t *>(q->rank.d);
+  int rc = hpgq::accum::for_parts(&b[0], nullptr, [&](const int32_t *ix1, const uint8_t *, int64_t np) {
+    const int64_t lo = ix1 - b[0].data_indices;
+    hipLaunchKernelGGL(ovl_plan_kernel, dim3(q->grid(8, (np + 255) / 256)), dim3(256), 0, q->stream, ix1,
+                       b[1].data_indices + lo, ins + lo, np, q->pos[0].d + lo, q->pos[1].d + lo, um + 1 + lo, rank + lo);
+  });
+  if (rc) return rc;
+  HPGQ_HIP_TRY(hipMemsetAsync(um, 0, 4, q->stream));
+  if ((rc = sum_in_place(q, &b[0], um + 1)) != HPGQ_OK || (rc = sum_in_place(q, &b[0], rank)) != HPGQ_OK) return rc;
+  int32_t *const h_m = static_cast<int32_t *>(q->h_extra());
+  HPGQ_HIP_TRY(hipMemcpyAsync(h_m, rank + n - 1, 4, hipMemcpyDeviceToHost, q->stream));
+  HPGQ_HIP_TRY(hipStreamSynchronize(q->stream));
+  const int64_t M = *h_m;
+  if (M < 0 || M > n) return HPGQ_E_HIP;
+  for (int m = 0; m < 2; ++m) {
+    rc = hpgq::cut::scan_and_copy(*q, &b[m], q->pos[m].d, q->kept[m].o_seq, q->kept[m].o_qual, m ? u2 : u1);
+    if (rc) return rc;
+  }
+  rc = hpgq::accum::for_parts(&b[0], nullptr, [&](const int32_t *ix1, const uint8_t *, int64_t np) {
+    const int64_t lo = ix1 - b[0].data_indices;
+    hipLaunchKernelGGL(ovl_compact_kernel, dim3(q->grid(8, (np + 255) / 256)), dim3(256), 0, q->stream, u1 + lo, u2 + lo,
+                       um + lo, rank + lo, ins + lo, np, lo, lo + np == n ? 1 : 0, q->kept[0].o_idx, q->kept[1].o_idx,
+                       q->merged.o_idx);
+    if (M)
+      hipLaunchKernelGGL(ovl_merge_kernel, dim3(q->grid(4, (np + kGroup - 1) / kGroup)), dim3(kWG), 0, q->stream, b[0].seq,
+                         b[0].quality, ix1, b[1].seq, b[1].quality, b[1].data_indices + lo, ins + lo, um + lo, np,
+                         q->merged.o_seq, q->merged.o_qual, q->d_scal);
+  });
+  *num_merged = M;
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -369,7 +582,7 @@ int hpgq_ovl_open(hpgq_ovl_t **ov, int device, int min_overlap, int max_mismatch
   hpgq_ovl *q = new hpgq_ovl;
   q->min_ov = min_overlap;
   q->max_mm = max_mismatches;
-  if ((rc = q->open(device, stream, kScalars + kFixScalars)) != HPGQ_OK) {
+  if ((rc = q->open(device, stream, kScalars + kFixScalars + kMergeScalars)) != HPGQ_OK) {
     hpgq_ovl_close(q);
     return rc;
   }
@@ -386,6 +599,10 @@ void hpgq_ovl_close(hpgq_ovl_t *q) {
   }
   q->ins.free();
   (void)hipFree(q->d_hist);
+  q->merged.free();
+  for (int m = 0; m < 2; ++m) q->uidx[m].free();
+  q->moff.free();
+  q->rank.free();
   delete q;
 }
 
@@ -421,6 +638,47 @@ int hpgq_ovl_batch_device(hpgq_ovl_t *q, const hpgq_batch_t *m1, const hpgq_batc
   if (rc) return rc;
   q->last_ins = n && (q->fix_on || q->hist_on) ? reinterpret_cast<const int32_t *>(q->ins.d) : nullptr;
   for (int m = 0; m < 2; ++m) q->kept[m].give(out[m], n);
+  return HPGQ_OK;
+}
+
+int hpgq_ovl_merge_device(hpgq_ovl_t *q, const hpgq_batch_t *m1, const hpgq_batch_t *m2, hpgq_batch_t *out1,
+                          hpgq_batch_t *out2, hpgq_batch_t *merged) {
+  if (!q || !pair_ok(m1, m2) || !out1 || !out2 || !merged || out1 == out2 || merged == out1 || merged == out2)
+    return HPGQ_E_INVALID;
+  if (m1->num_reads && (!m1->quality || !m2->quality)) return HPGQ_E_INVALID;
+  HPGQ_HIP_TRY(hipSetDevice(q->device));
+  const hpgq_batch_t b[2] = {*m1, *m2};   // (an input and an output may be the same struct)
+  const int64_t n = b[0].num_reads;
+  size_t held[2] = {0, 0};
+  for (int m = 0; m < 2; ++m) {
+    const int rc = hpgq::cut::Kept::held(*q, b[m], &held[m]);
+    if (rc) return rc;
+  }
+  if (held[0] + held[1] > (size_t)INT32_MAX) return HPGQ_E_INVALID;   // (the merged offsets are int32)
+  // a merged read has fewer bytes than its mates together
+  int rc = q->merged.room(*q, held[0] + held[1], n);
+  for (int m = 0; m < 2 && rc == HPGQ_OK; ++m) {
+    rc = q->kept[m].room(*q, held[m], n);
+    if (rc == HPGQ_OK && n) rc = q->pos[m].need(*q, n);
+    if (rc == HPGQ_OK && n) rc = q->uidx[m].need(*q, n + 1);
+  }
+  if (rc == HPGQ_OK && n) rc = q->moff.need(*q, n + 1);
+  if (rc == HPGQ_OK && n) rc = q->rank.need(*q, n);
+  if (rc == HPGQ_OK && n) rc = q->ins.need(*q, n);
+  if (rc == HPGQ_OK && n) rc = hpgq::cut::scan_room(*q, n);
+  if (rc) return rc;
+  int64_t M = 0;
+  if (n) {
+    rc = find(q, &b[0], &b[1], reinterpret_cast<int32_t *>(q->ins.d), nullptr, nullptr);
+    if (rc == HPGQ_OK) rc = merge(q, b, &M);
+    if (rc) return rc;
+  } else {
+    for (hpgq::cut::Kept *k : {&q->kept[0], &q->kept[1], &q->merged}) HPGQ_HIP_TRY(hipMemsetAsync(k->o_idx, 0, 4, q->stream));
+  }
+  q->last_ins = n ? reinterpret_cast<const int32_t *>(q->ins.d) : nullptr;
+  q->kept[0].give(out1, n - M);
+  q->kept[1].give(out2, n - M);
+  q->merged.give(merged, M);
   return HPGQ_OK;
 }
 
@@ -475,6 +733,18 @@ int hpgq_ovl_read_correct(hpgq_ovl_t *q, hpgq_ovl_correct_info_t *info) {
   info->phred = q->phred;
   info->high = q->high;
   info->low = q->low;
+  return HPGQ_OK;
+}
+
+int hpgq_ovl_read_merge(hpgq_ovl_t *q, hpgq_ovl_merge_info_t *info) {
+  if (!q || !info) return HPGQ_E_INVALID;
+  const int rc = q->settle();
+  if (rc) return rc;
+  const unsigned long long *s = q->h_scal + kScalars + kFixScalars;
+  info->merged_pairs = s[0];
+  info->merged_bases = s[1];
+  info->resolved[0] = s[2];
+  info->resolved[1] = s[3];
   return HPGQ_OK;
 }
 

@@ -1,5 +1,6 @@
 // hpgq_ovl_post.cpp — host side of `edit --clip-overlap`: the
-// overlap rule on one pair, and §2.14's correction of one pair.  HIP-free, no device.
+// overlap rule on one pair, §2.14's correction of one pair and §2.15's merge of
+// one pair.  HIP-free, no device.
 //
 // For a candidate insert length F, s1[k] faces s2[F - 1 - k] for k in
 // [max(0, F - n2), min(n1, F)).  F is admissible iff that range holds at least
@@ -80,4 +81,52 @@ extern "C" int64_t hpgq_ovl_correct(void *s1, void *q1, size_t n1, void *s2, voi
     changed[1] = done[1];
   }
   return (int64_t)done[0] + done[1];
+}
+
+// §2.15: the pair as one read of F bases.  Mate 1 before the facing positions,
+// the reverse complement of mate 2 behind them; at a facing position that does
+// not match, the base of strictly higher quality byte, mate 1's on a tie.
+extern "C" int64_t hpgq_ovl_merge(const void *s1, const void *q1, size_t n1, const void *s2, const void *q2, size_t n2,
+                                  int64_t F, void *seq_out, void *qual_out, uint32_t resolved[2]) {
+  if (((!s1 || !q1) && n1) || ((!s2 || !q2) && n2)) return -2;
+  if (resolved) resolved[0] = resolved[1] = 0;
+  if (F <= 0) return 0;
+  if (n1 > HPGQ_OVL_MAX_LEN || n2 > HPGQ_OVL_MAX_LEN) return -2;
+  const int64_t N1 = (int64_t)n1, N2 = (int64_t)n2;
+  const int64_t lo = F > N2 ? F - N2 : 0, hi = N1 < F ? N1 : F;
+  if (hi - lo < 8 || !seq_out || !qual_out) return -2;   // (no min_overlap admits this F)
+  const unsigned char *a = static_cast<const unsigned char *>(s1), *b = static_cast<const unsigned char *>(s2);
+  const unsigned char *qa = static_cast<const unsigned char *>(q1), *qb = static_cast<const unsigned char *>(q2);
+  unsigned char *m = static_cast<unsigned char *>(seq_out), *qm = static_cast<unsigned char *>(qual_out);
+  uint32_t done[2] = {0, 0};
+  for (int64_t p = 0; p < F; ++p) {
+    const int64_t j = F - 1 - p;
+    if (p < lo) {
+      m[p] = a[p];
+      qm[p] = qa[p];
+    } else if (p >= hi) {
+      const unsigned char c = comp(b[j]);
+      m[p] = c ? c : b[j];
+      qm[p] = qb[j];
+    } else {
+      const unsigned char ca = comp(a[p]), cb = comp(b[j]);
+      if (ca && b[j] == ca) {
+        m[p] = a[p];
+        qm[p] = qa[p] > qb[j] ? qa[p] : qb[j];
+      } else if (cb && (!ca || qb[j] > qa[p])) {
+        m[p] = cb;
+        qm[p] = qb[j];
+        ++done[1];
+      } else {
+        m[p] = a[p];
+        qm[p] = qa[p];
+        ++done[0];
+      }
+    }
+  }
+  if (resolved) {
+    resolved[0] = done[0];
+    resolved[1] = done[1];
+  }
+  return F;
 }

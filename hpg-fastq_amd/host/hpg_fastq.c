@@ -158,6 +158,8 @@ int main(int argc, char **argv) {
   /* --correct-overlap and --insert-size: one file each, beside it */
   if (r.ovl_fix_on && cli_report_ovl_correct(o, &r.ovl, &r.ovl_fix, mate_name[0])) rc = 1;
   if (r.ovl_insert_on && cli_report_insert(o, &r.ovl, r.ovl_inserts, mate_name[0])) rc = 1;
+  /* --merge-overlap: one more beside them */
+  if (r.ovl_merge_on && cli_report_merge(o, &r.ovl, &r.ovl_merge, mate_name[0])) rc = 1;
 
   if (!o->quiet) {
     printf("\n\nRESULTS\n");
@@ -177,6 +179,13 @@ int main(int argc, char **argv) {
       const char *ok = cmd == CMD_FILTER ? "passed" : "edit";
       if (cmd == CMD_EDIT) printf("Num. edited reads : %lu (mate 1)\n", (unsigned long)r.num_edited);
       if (r.ovl_on) printf("Num. overlap-clipped pairs : %lu\n", (unsigned long)r.ovl.clipped);
+      if (r.ovl_merge_on) {   /* (the pair lines below then count the pairs that did not merge) */
+        printf("Num. merged pairs : %lu (%s/edit_merged.fq)\n", (unsigned long)r.ovl_merge.merged_pairs, o->out_dirname);
+        if (p.filter_on) {
+          printf("\tNum. passed merged reads : %lu\n", (unsigned long)r.merged_passed);
+          printf("\tNum. failed merged reads : %lu\n", (unsigned long)r.merged_failed);
+        }
+      }
       if (r.ovl_fix_on) printf("Num. overlap-corrected pairs : %lu\n", (unsigned long)r.ovl_fix.corrected_pairs);
       if (r.clip_on) printf("Num. clipped reads : %lu (mate 1)\n", (unsigned long)r.clip[0].clipped);
       printf("Num. passed pairs : %lu (%s/%s_1.fq, %s/%s_2.fq)\n", (unsigned long)r.num_passed, o->out_dirname, ok,

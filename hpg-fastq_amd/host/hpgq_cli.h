@@ -55,6 +55,7 @@ typedef struct {
   int ovl_fix_high;         /* --correct-overlap-high: 1 .. 93 */
   int ovl_fix_low;          /* --correct-overlap-low: 0 .. 92, below the high quality */
   int ovl_insert_on;        /* --insert-size (§2.14): needs --clip-overlap */
+  int ovl_merge_on;         /* --merge-overlap (§2.15): needs --clip-overlap, excludes --correct-overlap */
   /* chaos game (old/main_hpg_fastq_old.c:185-189: --cg | --chaos-game, --k, --gs-filename) */
   int cg_on, k_cg;
   char *gs_filename;
@@ -131,6 +132,10 @@ typedef struct {
   hpgq_ovl_correct_info_t ovl_fix;
   int ovl_insert_on;        /* --insert-size: ovl_inserts holds the histogram, the workers' added */
   uint64_t ovl_inserts[HPGQ_OVL_INSERT_BINS];
+  int ovl_merge_on;         /* --merge-overlap: ovl_merge holds the merge's scalars, the workers' added; the merged
+                             * reads that passed / failed the filter come from the workers' single-end ctxs */
+  hpgq_ovl_merge_info_t ovl_merge;
+  uint64_t merged_passed, merged_failed;
   uint32_t *cg_seq, *cg_q;  /* --cg: table_seq / table_q [dim*dim] (malloc'd) */
   uint32_t cg_words;        /* fq_word_count */
   int cg_exact_calls;       /* chaos-game calls the exact simulation redid */
@@ -174,6 +179,9 @@ int cli_report_ovl(const cli_options_t *o, const hpgq_ovl_info_t *info, const ch
 /* --correct-overlap: <base>.overlap.correct.data from the pairs' and the correction's scalars */
 int cli_report_ovl_correct(const cli_options_t *o, const hpgq_ovl_info_t *info, const hpgq_ovl_correct_info_t *fix,
                            const char *base);
+/* --merge-overlap: <base>.overlap.merge.data from the pairs' and the merge's scalars */
+int cli_report_merge(const cli_options_t *o, const hpgq_ovl_info_t *info, const hpgq_ovl_merge_info_t *merge,
+                     const char *base);
 /* --insert-size: <base>.insert.size.data from the pairs' scalars and the histogram */
 int cli_report_insert(const cli_options_t *o, const hpgq_ovl_info_t *info, const uint64_t hist[HPGQ_OVL_INSERT_BINS],
                       const char *base);

@@ -12,7 +12,8 @@
  * (§2.9), --adapters / --adapter-file / --adapters-out (§2.11), --clip-adapters /
  * --clip-adapter-file / --clip-min-overlap (§2.12), --clip-overlap /
  * --clip-overlap-min / --clip-overlap-mismatches (§2.13), --correct-overlap /
- * --correct-overlap-high / --correct-overlap-low / --insert-size (§2.14).
+ * --correct-overlap-high / --correct-overlap-low / --insert-size (§2.14),
+ * --merge-overlap (§2.15).
  * --quality-encoding is accepted by every command
  * (quirk Q11).
  */
@@ -110,6 +111,7 @@ static void usage_status(const cli_options_t *o, int status) {
     printf("  --correct-overlap-high=<int>    Quality from which a base wins (1-93, default 30)\n");
     printf("  --correct-overlap-low=<int>     Quality up to which a base loses (0-92, below the high quality; default 14)\n");
     printf("  --insert-size                   With --clip-overlap: the histogram of the insert sizes found\n");
+    printf("  --merge-overlap                 With --clip-overlap: a pair whose mates overlap becomes one read (edit_merged.fq)\n");
   }
   printf("  --read-length-range=<string>    Read length range, eg. 80,110\n");
   printf("  --read-quality-range=<string>   Read quality range, eg. 20,40\n");
@@ -175,7 +177,7 @@ enum {
   O_KMERSOUT, O_CG, O_KCG, O_GS, O_GPUS, O_CGBATCH, O_CGOUT, O_GPUW, O_STREAMW, O_WHOOK, O_COPYT, O_PFT,
   O_FQ1, O_FQ2, O_INTER, O_QDIST, O_QDISTOUT, O_DUP, O_DUPOUT, O_OVER, O_OVERMIN, O_OVERTOP, O_OVERBYTES,
   O_ADAPT, O_ADAPTFILE, O_ADAPTOUT, O_CLIP, O_CLIPFILE, O_CLIPOV, O_OVL, O_OVLMIN, O_OVLMM,
-  O_FIX, O_FIXHIGH, O_FIXLOW, O_INSERT
+  O_FIX, O_FIXHIGH, O_FIXLOW, O_INSERT, O_MERGE
 };
 
 /* a whole-string decimal in [lo, hi] (u64), else the usage error */
@@ -278,6 +280,7 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
       {"correct-overlap-high", required_argument, 0, O_FIXHIGH},
       {"correct-overlap-low", required_argument, 0, O_FIXLOW},
       {"insert-size", no_argument, 0, O_INSERT},
+      {"merge-overlap", no_argument, 0, O_MERGE},
       {"quiet", no_argument, 0, O_QUIET},
       {"stream-writer", no_argument, 0, O_STREAMW},
       {"writer-test-hook", required_argument, 0, O_WHOOK},
@@ -394,6 +397,13 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
         if (c == O_FIXHIGH) o->ovl_fix_high = count_arg(o, "correct-overlap-high", optarg, 1, 93), fix_values = 1;
         if (c == O_FIXLOW) o->ovl_fix_low = count_arg(o, "correct-overlap-low", optarg, 0, 92), fix_values = 1;
         break;
+      case O_MERGE:
+        if (command != CMD_EDIT) {   /* one line, before anything is opened or written */
+          fprintf(stderr, "hpg-fastq: --merge-overlap is an option of the edit command, not of %s\n", o->command_name);
+          exit(1);
+        }
+        o->ovl_merge_on = 1;
+        break;
       case O_CG:
         if (command != CMD_STATS) usage(o);
         o->cg_on = 1;
@@ -476,6 +486,14 @@ cli_options_t *cli_parse(int command, const char *exec_name, int argc, char **ar
   }
   if (o->ovl_fix_on && o->ovl_fix_low >= o->ovl_fix_high) {
     printf("\nError: --correct-overlap-low (%d) must be below --correct-overlap-high (%d)\n", o->ovl_fix_low, o->ovl_fix_high);
+    usage_status(o, 1);
+  }
+  if (o->ovl_merge_on && !o->ovl_on) {
+    printf("\nError: --merge-overlap needs --clip-overlap\n");
+    usage_status(o, 1);
+  }
+  if (o->ovl_merge_on && o->ovl_fix_on) {
+    printf("\nError: --merge-overlap makes --correct-overlap void: a merged read is the same with and without it\n");
     usage_status(o, 1);
   }
   if (fq1) o->in_filename = fq1;
@@ -608,6 +626,7 @@ void cli_display(const cli_options_t *o) {
   if (o->ovl_fix_on)
     printf("\tOverlap correction   : high quality %d, low quality %d (--correct-overlap)\n", o->ovl_fix_high, o->ovl_fix_low);
   if (o->ovl_insert_on) printf("\tInsert sizes         : counted (--insert-size)\n");
+  if (o->ovl_merge_on) printf("\tOverlap merging      : pairs with an overlap become one read (--merge-overlap)\n");
   if (o->clip_on)
     printf("\tAdapter clipping     : %d probes, min overlap %d (--clip-adapters)\n", o->adapter_n, o->clip_min_overlap);
   printf("\n%s options\n", o->command == CMD_EDIT ? "Edit and filter" : "Filter");

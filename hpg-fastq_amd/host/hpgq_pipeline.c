@@ -94,9 +94,9 @@ typedef struct {
   /* edit: the chunk's output records per mate and class ([2 m + c]; c: 0
    * edit.fq / passed, 1 failed), assembled by the GPU worker so the writer only
    * writes them in order */
-  char *out[4];
-  size_t out_cap[4], out_len[4];
-  uint64_t out_n[4];
+  char *out[6];       /* ([4], [5]: --merge-overlap's merged reads, edit_merged.fq / failed_merged.fq) */
+  size_t out_cap[6], out_len[6];
+  uint64_t out_n[6];
   /* mapped outputs: this chunk's copy parts (copy_part_t[MAX_COPIERS]) and
    * how many are still being copied (state 3 until the last one is done) */
   void *parts;
@@ -116,7 +116,7 @@ typedef struct {
    * --fq2); the output files per mate and class ([2 m + c] like slot_t.out:
    * passed / edit, failed; NULL: not written) and the first pair out of step */
   int nmates, nsides;
-  FILE *out[4];
+  FILE *out[6];          /* ([4], [5]: edit_merged.fq, failed_merged.fq) */
   uint64_t written_pass, written_fail;
   int64_t bad_pair, bad_chunk;
   char pairing_msg[512];
@@ -352,6 +352,8 @@ static int write_slot(pipe_t *P, slot_t *s) {
         if (v.f[c] && s->out_len[2 * m + c] && write_span(v.f[c], s->out[2 * m + c], s->out_len[2 * m + c]))
           return -1;
     }
+    for (int c = 4; c < 6; ++c)   /* (--merge-overlap: the merged reads) */
+      if (P->out[c] && s->out_len[c] && write_span(P->out[c], s->out[c], s->out_len[c])) return -1;
     P->written_pass += s->out_n[0];
     P->written_fail += s->out_n[1];
     return 0;
@@ -464,6 +466,105 @@ static int assemble_edit(pipe_t *P, slot_t *s) {
     }
     for (int c = 0; c < 2; ++c) s->out_len[2 * m + c] = v.f[c] ? (size_t)(d[c] - out[c]) : 0;
   }
+  return 0;
+}
+
+/* room for `need` bytes in output k of the slot */
+static int out_room(slot_t *s, int k, size_t need) {
+  if (s->out_cap[k] >= need) return 0;
+  free(s->out[k]);
+  s->out_cap[k] = need + need / 8;
+  s->out[k] = malloc(s->out_cap[k]);
+  if (!s->out[k]) {
+    s->out_cap[k] = 0;
+    return HPGQ_E_NOMEM;
+  }
+  return 0;
+}
+
+/* one output record: header line, keep bases, '+' line, keep qualities */
+static inline char *put_record(char *o, const char *hdr, uint32_t hl, const char *seq, const char *plus, uint32_t pl,
+                               const char *qual, uint32_t keep) {
+  memcpy(o, hdr, hl);
+  o += hl;
+  memcpy(o, seq, keep);
+  o += keep;
+  *o++ = '\n';
+  memcpy(o, plus, pl);
+  o += pl;
+  memcpy(o, qual, keep);
+  o += keep;
+  *o++ = '\n';
+  return o;
+}
+
+/* edit --merge-overlap: assemble_edit over a unit whose pairs
+ * split in two.  ins: the unit's F*.  Pair i with ins[i] <= 0 is the next
+ * unmerged pair: its mates go to edit_1/2 or failed_1/2 from the paired ctx's
+ * mask, trims and kept offsets at that rank (n_un of them).  A pair with
+ * ins[i] > 0 is the next merged read: mate 1's header and '+' line as they
+ * stand, between them the merged bases and qualities, rebuilt from the text by
+ * the host rule (hpgq_ovl_merge), trimmed and classed by the merged ctx's
+ * results at that rank.  (Its unmerged branch is assemble_edit's record path
+ * once more, through out_room and put_record; assemble_edit itself is left as
+ * it was and could use the two helpers as well.) */
+static int assemble_merge(pipe_t *P, slot_t *s, const int32_t *ins, int64_t n_un, const uint8_t *mmask,
+                          const uint32_t *mtrim, const int32_t *midx) {
+  const int filter_on = P->o->filter_on;
+  mate_view_t v[2] = {mate_view(P, s, 0), mate_view(P, s, 1)};
+  for (int m = 0; m < 2; ++m) {   /* (the engine's results are n_un long, the record offsets the unit's) */
+    v[m].trim = s->trim + (size_t)m * (size_t)n_un;
+    v[m].idx = s->idx + (size_t)m * (size_t)(n_un + 1);
+  }
+  char *d[6] = {NULL, NULL, NULL, NULL, NULL, NULL};
+  for (int k = 0; k < 6; ++k) {
+    s->out_len[k] = 0;
+    s->out_n[k] = 0;
+    if (!P->out[k]) continue;
+    const int rc = out_room(s, k, k < 4 ? v[k / 2].use + 64 : v[0].use + v[1].use + 64);
+    if (rc) return rc;
+    d[k] = s->out[k];
+  }
+  static __thread unsigned char mseq[2 * HPGQ_OVL_MAX_LEN], mqual[2 * HPGQ_OVL_MAX_LEN];
+  int64_t u = 0, g = 0;
+  for (int64_t i = 0; i < s->nreads; ++i) {
+    const int64_t r0 = v[0].first + i * v[0].stride;
+    if (ins[i] > 0) {
+      const int c = mmask[g] != 0 || !filter_on ? 0 : 1;
+      if (d[4 + c]) {
+        const char *seq[2], *qual[2];
+        size_t len[2];
+        for (int m = 0; m < 2; ++m) {
+          const int64_t r = v[m].first + i * v[m].stride;
+          seq[m] = v[m].buf + v[m].ss[r];
+          qual[m] = v[m].buf + v[m].qs[r];
+          len[m] = v[m].ps[r] - v[m].ss[r] - 1;
+          if (len[m] && seq[m][len[m] - 1] == '\r') --len[m];
+        }
+        const uint32_t F = (uint32_t)ins[i], ts = mtrim[g] & 0xFFFFu, te = mtrim[g] >> 16;
+        if ((uint32_t)(midx[g + 1] - midx[g]) != F || ts + te > F ||
+            hpgq_ovl_merge(seq[0], qual[0], len[0], seq[1], qual[1], len[1], ins[i], mseq, mqual, NULL) != ins[i])
+          return HPGQ_E_INVALID;
+        d[4 + c] = put_record(d[4 + c], v[0].buf + v[0].rs[r0], v[0].ss[r0] - v[0].rs[r0], (const char *)mseq + ts,
+                              v[0].buf + v[0].ps[r0], v[0].qs[r0] - v[0].ps[r0], (const char *)mqual + ts, F - ts - te);
+        s->out_n[4 + c]++;
+      }
+      ++g;
+      continue;
+    }
+    const int c = s->mask[u] != 0 || !filter_on ? 0 : 1;
+    for (int m = 0; m < 2; ++m) {
+      if (!d[2 * m + c]) continue;
+      const int64_t r = v[m].first + i * v[m].stride;
+      const uint32_t ts = v[m].trim[u] & 0xFFFFu, te = v[m].trim[u] >> 16;
+      const uint32_t keep = (uint32_t)(v[m].idx[u + 1] - v[m].idx[u]) - ts - te;
+      d[2 * m + c] = put_record(d[2 * m + c], v[m].buf + v[m].rs[r], v[m].ss[r] - v[m].rs[r], v[m].buf + v[m].ss[r] + ts,
+                                v[m].buf + v[m].ps[r], v[m].qs[r] - v[m].ps[r], v[m].buf + v[m].qs[r] + ts, keep);
+      s->out_n[2 * m + c]++;
+    }
+    ++u;
+  }
+  for (int k = 0; k < 6; ++k) s->out_len[k] = d[k] ? (size_t)(d[k] - s->out[k]) : 0;
   return 0;
 }
 
@@ -815,8 +916,17 @@ typedef struct {
   hpgq_adapt_t *ad[2];    /* --adapters: one table per mate, on the ctx stream */
   hpgq_clip_t *cl[2];     /* --clip-adapters: one handle per mate, on the ctx stream */
   hpgq_ovl_t *ov;         /* --clip-overlap: one handle for the pair, on the ctx stream */
-  int32_t *h_ins;         /* --correct-overlap: the unit's F* on the host ([ins_cap]), for correct_text */
+  int32_t *h_ins;         /* --correct-overlap, --merge-overlap: the unit's F* on the host ([ins_cap]) */
   size_t ins_cap;
+  /* --merge-overlap (§2.15): a single-end ctx for the merged reads on the paired ctx's stream (the run's
+   * parameters with paired = 0; it runs behind the merge and the paired ctx), its mask and trims on the device
+   * and, page-locked on the host, with the merged reads' kept offsets ([mcap], [mcap], [mcap + 1]) */
+  hpgq_params_t p2;
+  hpgq_ctx_t *ctx2;
+  uint8_t *d_mask2, *h_mmask;
+  uint32_t *d_trim2, *h_mtrim;
+  int32_t *h_midx;
+  size_t mcap;
   hpgq_cgr_t *cg;
   uint8_t *d_mask;
   uint32_t *d_trim;
@@ -852,6 +962,11 @@ static int worker_open(worker_t *W) {
   if (rc == 0 && o->ovl_fix_on)
     rc = hpgq_ovl_set_correct(W->ov, 1, o->quality_encoding_value, o->ovl_fix_high, o->ovl_fix_low);
   if (rc == 0 && o->ovl_insert_on) rc = hpgq_ovl_count_inserts(W->ov, 1);
+  if (rc == 0 && o->ovl_merge_on) {
+    W->p2 = *W->p;
+    W->p2.paired = 0;
+    rc = hpgq_open_on_stream(&W->ctx2, W->device, &W->p2, hpgq_stream(W->ctx));
+  }
   /* --clip-adapters cuts each mate on its own before the engine sees it */
   for (int m = 0; m < W->P->nmates && rc == 0 && o->clip_on; ++m) {
     const char *probes[HPGQ_ADAPT_MAX_PROBES];
@@ -889,6 +1004,12 @@ static void worker_close(worker_t *W) {
   hpgq_clip_close(W->cl[1]);
   hpgq_ovl_close(W->ov);
   free(W->h_ins);
+  hpgq_device_free(W->d_mask2);
+  hpgq_device_free(W->d_trim2);
+  hpgq_host_free(W->h_mmask);
+  hpgq_host_free(W->h_mtrim);
+  hpgq_host_free(W->h_midx);
+  hpgq_close(W->ctx2);
   hpgq_dup_close(W->dp[0]);
   hpgq_dup_close(W->dp[1]);
   hpgq_cgr_close(W->cg);
@@ -1010,11 +1131,17 @@ static int worker_chunk(worker_t *W, slot_t *s) {
   if (rc || b[0].num_reads == 0) return rc;
   /* --clip-overlap: from here on the pair is the kept reads, in buffers the
    * handle owns until its next chunk; the probes below see what it kept */
-  if (W->ov && (rc = hpgq_ovl_batch_device(W->ov, &b[0], &b[1], &b[0], &b[1])) != 0) return rc;
+  const size_t na = (size_t)b[0].num_reads;   /* the unit's reads (pairs): what the texts hold */
+  const int merging = W->ov && o->ovl_merge_on;
+  hpgq_batch_t bm = {0, NULL, NULL, NULL};
+  /* --merge-overlap (§2.15): the pairs without an overlap go on as pairs, uncut; the others as one read each */
+  if (merging) {
+    if ((rc = hpgq_ovl_merge_device(W->ov, &b[0], &b[1], &b[0], &b[1], &bm)) != 0) return rc;
+  } else if (W->ov && (rc = hpgq_ovl_batch_device(W->ov, &b[0], &b[1], &b[0], &b[1])) != 0) return rc;
   /* --clip-adapters: from here on the batch is the kept reads, in buffers the
    * handle owns until its next chunk (this chunk's hpgq_sync comes before that) */
   for (int m = 0; m < nm && W->cl[m]; ++m)
-    if ((rc = hpgq_clip_batch_device(W->cl[m], &b[m], &b[m])) != 0) return rc;
+    if (b[m].num_reads && (rc = hpgq_clip_batch_device(W->cl[m], &b[m], &b[m])) != 0) return rc;
   const size_t n = (size_t)b[0].num_reads;
   if (need_mask && n > W->dcap) {
     hpgq_device_free(W->d_mask);
@@ -1033,8 +1160,34 @@ static int worker_chunk(worker_t *W, slot_t *s) {
     for (int m = 0; m < nm && rc == 0 && W->qd[m]; ++m) rc = hpgq_qdist_reserve_length(W->qd[m], ml);
     for (int m = 0; m < nm && rc == 0 && W->ad[m]; ++m) rc = hpgq_adapt_reserve_length(W->ad[m], ml);
   }
-  if (rc == 0)
+  if (rc == 0 && (n || !merging))   /* (--merge-overlap: every pair of the unit may have merged) */
     rc = hpgq_run_device(W->ctx, &b[0], nm == 2 ? &b[1] : NULL, need_mask ? W->d_mask : NULL, edit ? W->d_trim : NULL);
+  /* the merged reads through the single-end ctx: no adapter clip, everything behind base F* is gone */
+  const size_t M = (size_t)bm.num_reads;
+  if (rc == 0 && M) {
+    if (M > W->mcap) {
+      hpgq_device_free(W->d_mask2);
+      hpgq_device_free(W->d_trim2);
+      hpgq_host_free(W->h_mmask);
+      hpgq_host_free(W->h_mtrim);
+      hpgq_host_free(W->h_midx);
+      W->d_mask2 = W->h_mmask = NULL;
+      W->d_trim2 = W->h_mtrim = NULL;
+      W->h_midx = NULL;
+      W->mcap = M + M / 4 + 1024;
+      rc = hpgq_device_alloc(W->device, (void **)&W->d_mask2, W->mcap);
+      if (rc == 0) rc = hpgq_device_alloc(W->device, (void **)&W->d_trim2, W->mcap * 4);
+      if (rc == 0) rc = hpgq_host_alloc((void **)&W->h_mmask, W->mcap);
+      if (rc == 0) rc = hpgq_host_alloc((void **)&W->h_mtrim, W->mcap * 4);
+      if (rc == 0) rc = hpgq_host_alloc((void **)&W->h_midx, (W->mcap + 1) * 4);
+      if (rc) W->mcap = 0;
+    }
+    if (rc == 0) rc = hpgq_reserve_length(W->ctx2, 2 * HPGQ_OVL_MAX_LEN - 8);
+    if (rc == 0) rc = hpgq_run_device(W->ctx2, &bm, NULL, W->d_mask2, W->d_trim2);
+    if (rc == 0) rc = hpgq_copy_to_host(W->ctx2, W->h_mmask, W->d_mask2, M);
+    if (rc == 0) rc = hpgq_copy_to_host(W->ctx2, W->h_mtrim, W->d_trim2, M * 4);
+    if (rc == 0) rc = hpgq_copy_to_host(W->ctx2, W->h_midx, bm.data_indices, (M + 1) * 4);
+  }
   if (rc == 0 && W->km) rc = hpgq_kmers_count_device(W->km, &b[0], o->filter_on ? W->d_mask : NULL);
   for (int m = 0; m < nm && rc == 0 && W->qd[m]; ++m)   /* (paired: the pair mask for both mates) */
     rc = hpgq_qdist_count_device(W->qd[m], &b[m], o->filter_on ? W->d_mask : NULL);
@@ -1043,9 +1196,9 @@ static int worker_chunk(worker_t *W, slot_t *s) {
   for (int m = 0; m < nm && rc == 0 && W->dp[m]; ++m)   /* (the same reads, the same mask) */
     rc = hpgq_dup_count_device(W->dp[m], &b[m], o->filter_on ? W->d_mask : NULL);
   if (rc == 0 && writes) {
-    s->nreads = b[0].num_reads;
-    if (ensure_results(s, b[0].num_reads, nm)) rc = HPGQ_E_NOMEM;
-    if (rc == 0) rc = hpgq_copy_to_host(W->ctx, s->mask, W->d_mask, n);
+    s->nreads = (int64_t)na;
+    if (ensure_results(s, (int64_t)na, nm)) rc = HPGQ_E_NOMEM;
+    if (rc == 0 && n) rc = hpgq_copy_to_host(W->ctx, s->mask, W->d_mask, n);
     if (rc == 0 && edit) {   /* (trim_out: mate m of read i at [m n + i]) */
       rc = hpgq_copy_to_host(W->ctx, s->trim, W->d_trim, n * 4 * (size_t)nm);
       for (int m = 0; m < nm && rc == 0; ++m)
@@ -1053,33 +1206,35 @@ static int worker_chunk(worker_t *W, slot_t *s) {
     }
     /* the record offsets: an interleaved text's 2 n in text order, else mate 2's after mate 1's */
     for (int m = 0; m < ns && rc == 0; ++m)
-      rc = hpgq_parse_records(W->ps[m], s->rec_start + m * n, s->seq_start + m * n, s->plus_start + m * n,
-                              s->qual_start + m * n);
+      rc = hpgq_parse_records(W->ps[m], s->rec_start + m * na, s->seq_start + m * na, s->plus_start + m * na,
+                              s->qual_start + m * na);
     /* --correct-overlap: the unit's F* for correct_text */
-    if (rc == 0 && W->ov && o->ovl_fix_on) {
+    if (rc == 0 && W->ov && (o->ovl_fix_on || merging)) {
       const int32_t *d_ins = NULL;
       rc = hpgq_ovl_last_inserts(W->ov, &d_ins);
-      if (rc == 0 && n > W->ins_cap) {
+      if (rc == 0 && na > W->ins_cap) {
         free(W->h_ins);
-        W->ins_cap = n + n / 4 + 1024;
+        W->ins_cap = na + na / 4 + 1024;
         W->h_ins = malloc(W->ins_cap * sizeof(int32_t));
         if (!W->h_ins) W->ins_cap = 0, rc = HPGQ_E_NOMEM;
       }
-      if (rc == 0) rc = hpgq_copy_to_host(W->ctx, W->h_ins, d_ins, n * sizeof(int32_t));
+      if (rc == 0) rc = hpgq_copy_to_host(W->ctx, W->h_ins, d_ins, na * sizeof(int32_t));
     }
   }
   trace_at(P, s->chunk, 3, -1);
   if (rc == 0) rc = hpgq_sync(W->ctx);
+  if (rc == 0 && M) rc = hpgq_sync(W->ctx2);
   trace_at(P, s->chunk, 6, -1);
   if (rc == 0 && writes && W->ov && o->ovl_fix_on) rc = correct_text(P, s, W->h_ins);
-  if (rc == 0 && edit && !P->mmap_out) rc = assemble_edit(P, s);
+  if (rc == 0 && edit && !P->mmap_out)
+    rc = merging ? assemble_merge(P, s, W->h_ins, (int64_t)n, W->h_mmask, W->h_mtrim, W->h_midx) : assemble_edit(P, s);
   if (rc == 0 && W->cg) {   /* after the parse and the mask; settled before the next parse reuses b */
     rc = hpgq_cgr_fill_device(W->cg, &b[0], o->filter_on ? W->d_mask : NULL,
                               o->filter_on ? HPGQ_CGR_ONLY_VALID_READS : HPGQ_CGR_ALL_READS);
     if (rc == 0) rc = hpgq_cgr_sync(W->cg);
     if (rc == 0) W->cg_exact_calls += hpgq_cgr_last_exact(W->cg);
   }
-  W->num_reads += (uint64_t)b[0].num_reads;
+  W->num_reads += (uint64_t)na;
   return rc;
 }
 
@@ -1226,6 +1381,15 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
       P.out[i] = fopen(path, "w+");
       if (!P.out[i]) rc = HPGQ_E_INVALID;
       else setvbuf(P.out[i], NULL, _IOFBF, 16 << 20);
+    }
+    /* --merge-overlap: the merged reads' own pair of files */
+    for (int c = 0; c < 2 && rc == 0 && o->ovl_merge_on; ++c) {
+      char path[4096];
+      if (c && !o->filter_on) continue;
+      snprintf(path, sizeof(path), "%s/%s_merged.fq", o->out_dirname, c ? "failed" : "edit");
+      P.out[4 + c] = fopen(path, "w+");
+      if (!P.out[4 + c]) rc = HPGQ_E_INVALID;
+      else setvbuf(P.out[4 + c], NULL, _IOFBF, 16 << 20);
     }
     /* (paired output goes through the stream writer: the mapped path is two-output) */
     if (rc == 0 && !o->stream_writer && !p->paired) {   /* not mappable (1): the writer thread */
@@ -1378,6 +1542,26 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
     res->ovl_fix.high = fix.high;
     res->ovl_fix.low = fix.low;
   }
+  /* --merge-overlap: the workers' four scalars added, and what their single-end ctxs counted */
+  for (int w = 0; w < G && rc == 0 && o->ovl_merge_on; ++w) {
+    hpgq_ovl_merge_info_t mi;
+    res->ovl_merge_on = 1;
+    rc = hpgq_ovl_read_merge(W[w].ov, &mi);
+    if (rc) break;
+    res->ovl_merge.merged_pairs += mi.merged_pairs;
+    res->ovl_merge.merged_bases += mi.merged_bases;
+    res->ovl_merge.resolved[0] += mi.resolved[0];
+    res->ovl_merge.resolved[1] += mi.resolved[1];
+    const size_t nc = hpgq_counters_size(W[w].ctx2);
+    uint64_t *part = calloc(nc, sizeof(uint64_t));
+    if (!part) rc = HPGQ_E_NOMEM;
+    if (rc == 0) rc = hpgq_read_counters(W[w].ctx2, part, nc);
+    if (rc == 0) {
+      res->merged_passed += part[HPGQ_S_NUM_PASSED];
+      res->merged_failed += part[HPGQ_S_NUM_FAILED];
+    }
+    free(part);
+  }
   for (int w = 0; w < G && rc == 0 && o->ovl_insert_on; ++w) {
     uint64_t *hist = malloc(sizeof(uint64_t) * HPGQ_OVL_INSERT_BINS);
     res->ovl_insert_on = 1;
@@ -1463,14 +1647,14 @@ int cli_run(const cli_options_t *o, const hpgq_params_t *p, cli_result_t *res) {
 done:
   if (P.ncopiers) stop_copiers(&P);
   if (P.mmap_out) unmap_outputs(&P, &rc);
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < 6; ++i)
     if (P.out[i]) fclose(P.out[i]);
   for (int i = 0; i < P.nslots; ++i) {
     hpgq_host_free(P.slot[i].buf);
     hpgq_host_free(P.slot[i].buf2);
     free_results(&P.slot[i]);
     free(P.slot[i].parts);
-    for (int c = 0; c < 4; ++c) free(P.slot[i].out[c]);
+    for (int c = 0; c < 6; ++c) free(P.slot[i].out[c]);
   }
   reader_close(P.rd);
   close_inputs(in);

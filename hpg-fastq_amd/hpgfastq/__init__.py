@@ -17,7 +17,7 @@ from .engine import Engine, ChaosGame, Kmers, Parser, Signature, QualityDist, qd
 from .engine import Duplication, dup_fingerprint, dup_levels_of, dup_level_bounds, dup_top_of  # noqa: F401
 from .engine import AdapterContent, adapt_add, adapt_find, adapt_defaults  # noqa: F401
 from .engine import AdapterClip, clip_find  # noqa: F401
-from .engine import OverlapClip, ovl_find, ovl_correct  # noqa: F401
+from .engine import OverlapClip, ovl_find, ovl_correct, ovl_merge  # noqa: F401
 from .engine import (cgr_write_gs, cgr_load_gs, cgr_table_dif, cgr_dif_stats,  # noqa: F401
                      cgr_normalize_quality, cgr_write_pgm, cgr_write_images)
 from .options import parse_range, filter_params, edit_params, stats_params  # noqa: F401

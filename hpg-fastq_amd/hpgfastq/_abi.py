@@ -117,6 +117,10 @@ class OvlCorrectInfo(C.Structure):
                 ("phred", C.c_int32), ("high", C.c_int32), ("low", C.c_int32)]
 
 
+class OvlMergeInfo(C.Structure):
+    _fields_ = [("merged_pairs", C.c_uint64), ("merged_bases", C.c_uint64), ("resolved", C.c_uint64 * 2)]
+
+
 class GsInfo(C.Structure):
     _fields_ = [("words", C.c_uint64), ("bases", C.c_uint64), ("ns", C.c_uint64),
                 ("sequences", C.c_uint64)]
@@ -142,6 +146,7 @@ _SIGS = [
     ("hpgq_params_init", None, [C.POINTER(Params)]),
     ("hpgq_counters_summary", C.c_int, [C.c_void_p, C.c_int, C.POINTER(Summary)]),
     ("hpgq_open", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Params)]),
+    ("hpgq_open_on_stream", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Params), C.c_void_p]),
     ("hpgq_close", None, [C.c_void_p]),
     ("hpgq_run_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Batch),
                                   C.c_void_p, C.c_void_p]),
@@ -277,6 +282,11 @@ _SIGS = [
     ("hpgq_ovl_read_correct", C.c_int, [C.c_void_p, C.POINTER(OvlCorrectInfo)]),
     ("hpgq_ovl_read_inserts", C.c_int, [C.c_void_p, C.c_void_p]),
     ("hpgq_ovl_last_inserts", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("hpgq_ovl_merge_device", C.c_int, [C.c_void_p, C.POINTER(Batch), C.POINTER(Batch), C.POINTER(Batch), C.POINTER(Batch),
+                                        C.POINTER(Batch)]),
+    ("hpgq_ovl_read_merge", C.c_int, [C.c_void_p, C.POINTER(OvlMergeInfo)]),
+    ("hpgq_ovl_merge", C.c_int64, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
+                                   C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     ("hpgq_ovl_correct", C.c_int64, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64,
                                      C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32)]),
     ("hpgq_synth_length", C.c_int32, [C.POINTER(Synth), C.c_int64]),

@@ -9,7 +9,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, AdaptInfo, ClipInfo, OvlInfo, OvlCorrectInfo, OVL_INSERT_BINS,
+from ._abi import (lib, check, Params, Batch, Summary, GsInfo, QdistRow, DupLevels, AdaptInfo, ClipInfo, OvlInfo, OvlCorrectInfo, OvlMergeInfo, OVL_INSERT_BINS,
                    counters_len,
                    CGR_ALL_READS, ROUTES, E_PAIRING, QDIST_VALUES, DUP_LEVELS, HpgqError)
 
@@ -556,7 +556,7 @@ class OverlapClip(_Handle):
 
     def last_inserts_ptr(self):
         """hpgq_ovl_last_inserts: the device pointer (int) to the F* (int32 [n]) of the last
-        clip_batch while a switch was on, None otherwise; valid until the next call."""
+        clip_batch while a switch was on, or of the last merge_batch; None otherwise; valid until the next call."""
         p = C.c_void_p()
         self._call("last_inserts", C.byref(p))
         return p.value
@@ -577,6 +577,22 @@ class OverlapClip(_Handle):
         out1, out2 = Batch(), Batch()
         self._call("batch_device", C.byref(mate1), C.byref(mate2), C.byref(out1), C.byref(out2))
         return out1, out2
+
+    def merge_batch(self, mate1, mate2):
+        """hpgq_ovl_merge_device: (out1, out2, merged), the pairs
+        without an overlap uncut as two Batches and the pairs with F* > 0 as one
+        read each, all three compacted, in input order, over buffers the handle
+        owns, valid until the next call or close.  last_inserts_ptr() is valid
+        after it whatever the switches."""
+        out1, out2, merged = Batch(), Batch(), Batch()
+        self._call("merge_device", C.byref(mate1), C.byref(mate2), C.byref(out1), C.byref(out2), C.byref(merged))
+        return out1, out2, merged
+
+    def merge_info(self):
+        """dict(merged_pairs, merged_bases, resolved [2]); synchronises."""
+        i = OvlMergeInfo()
+        self._call("read_merge", C.byref(i))
+        return dict(merged_pairs=int(i.merged_pairs), merged_bases=int(i.merged_bases), resolved=[int(x) for x in i.resolved])
 
     def info(self):
         """dict(pairs, skipped, overlapping, clipped, bases_removed [2], min_overlap, max_mismatches); synchronises."""
@@ -612,6 +628,23 @@ def ovl_correct(s1, q1, s2, q2, F, phred=33, high=30, low=14):
     out = [b.raw[:len(x)] for b, x in zip(bufs, (s1, q1, s2, q2))]
     assert r == changed[0] + changed[1]
     return (*out, [int(changed[0]), int(changed[1])])
+
+
+def ovl_merge(s1, q1, s2, q2, F):
+    """hpgq_ovl_merge: §2.15's merged read of one pair whose F* is F.  Returns
+    (seq, qual, [bases resolved by mate 1, by mate 2]), both of F bytes (empty
+    for F <= 0; HpgqError -1 for an F the pair cannot have)."""
+    s1, q1, s2, q2 = (bytes(x) for x in (s1, q1, s2, q2))
+    if len(s1) != len(q1) or len(s2) != len(q2):
+        raise ValueError("a mate's quality is as long as its sequence")
+    n = max(int(F), 0)
+    seq, qual = C.create_string_buffer(max(n, 1)), C.create_string_buffer(max(n, 1))
+    resolved = (C.c_uint32 * 2)()
+    r = lib.hpgq_ovl_merge(s1, q1, len(s1), s2, q2, len(s2), int(F), seq, qual, resolved)
+    if r == -2:
+        raise HpgqError(-1, "hpgq_ovl_merge")
+    assert r == n
+    return seq.raw[:n], qual.raw[:n], [int(resolved[0]), int(resolved[1])]
 
 
 def _levels_dict(lv):

@@ -214,6 +214,11 @@ typedef struct hpgq_ctx hpgq_ctx_t;
 
 /* Open a ctx on HIP device `device` (its own stream, counters zeroed). */
 int  hpgq_open(hpgq_ctx_t **ctx, int device, const hpgq_params_t *p);
+/* The same on the caller's HIP stream (hipStream_t, not NULL: HPGQ_E_INVALID),
+ * which the ctx borrows and never destroys: a second ctx on hpgq_stream() of
+ * the first runs in the first one's order (the CLI's single-end ctx for the
+ * merged reads).  The stream must outlive the ctx. */
+int  hpgq_open_on_stream(hpgq_ctx_t **ctx, int device, const hpgq_params_t *p, void *stream);
 void hpgq_close(hpgq_ctx_t *ctx);
 
 /*
@@ -944,6 +949,50 @@ int  hpgq_ovl_last_inserts(hpgq_ovl_t *ov, const int32_t **inserts);
  * lengths (a mate longer than HPGQ_OVL_MAX_LEN, fewer than 8 facing bytes). */
 int64_t hpgq_ovl_correct(void *s1, void *q1, size_t n1, void *s2, void *q2, size_t n2, int64_t F,
                          int phred, int high, int low, uint32_t changed[2]);
+
+/*
+ * edit --merge-overlap (build-defined): a pair with F = F* > 0
+ * becomes one read m[0, F), QM[0, F); every other pair passes through uncut
+ * and unchanged.  rc(b) is comp(b) for A C G T and b itself for every other
+ * byte.  With lo, hi as above and j = F - 1 - p:
+ *   p <  lo: m[p] = s1[p],      QM[p] = Q1[p];
+ *   p >= hi: m[p] = rc(s2[j]),  QM[p] = Q2[j];
+ *   lo <= p < hi (a facing position):
+ *     1. a match (the rule above): m[p] = s1[p], QM[p] = max(Q1[p], Q2[j]);
+ *     2. else, with a1 / a2 = "s1[p] / s2[j] is one of A C G T", mate 2 wins iff
+ *        a2 && (!a1 || Q2[j] > Q1[p]) (unsigned bytes, a tie goes to mate 1):
+ *        m[p] = comp(s2[j]), QM[p] = Q2[j], one base resolved by mate 2;
+ *     3. else m[p] = s1[p], QM[p] = Q1[p], one base resolved by mate 1.
+ * The merge reads the inputs: it never corrects, never counts §2.14's scalars
+ * and ignores the correction switch (merging a corrected pair gives the same
+ * bytes).  The find pass of a merge call counts §2.13's scalars and, while
+ * counting is on, the histogram, as hpgq_ovl_batch_device's does.
+ */
+typedef struct hpgq_ovl_merge_info {
+  uint64_t merged_pairs, merged_bases, resolved[2];   /* pairs with F* > 0; the sum of their F*; bases per winning mate */
+} hpgq_ovl_merge_info_t;
+/* find, then three compacted batches in buffers the handle owns (the contract
+ * of hpgq_ovl_batch_device): out1 / out2 the pairs that do not merge, uncut,
+ * in input order; merged the merged reads in input order.  out1 / out2 may be
+ * m1 / m2; the inputs are never written.  hpgq_ovl_last_inserts is valid after
+ * this call whatever the switches: pair i merged iff F*[i] > 0.  Waits for the
+ * stream three times, once more than hpgq_ovl_batch_device: for each input's
+ * size, and for the number of merged pairs.
+ * HPGQ_E_INVALID before any device work for the argument errors of
+ * hpgq_ovl_batch_device and a NULL merged; for inputs of more than INT32_MAX
+ * bytes together (the merged offsets are int32) after the two waits that
+ * fetch the inputs' sizes, before anything is allocated or launched. */
+int  hpgq_ovl_merge_device(hpgq_ovl_t *ov, const hpgq_batch_t *m1, const hpgq_batch_t *m2,
+                           hpgq_batch_t *out1, hpgq_batch_t *out2, hpgq_batch_t *merged);
+/* the merge's scalars since open or reset (hpgq_ovl_reset zeroes them).  Synchronises. */
+int  hpgq_ovl_read_merge(hpgq_ovl_t *ov, hpgq_ovl_merge_info_t *info);
+/* Host only, no device (csrc/hpgq_ovl_post.cpp): the merged read of one pair
+ * whose F* is F, F bytes each into seq_out and qual_out.  Returns F and sets
+ * resolved[0] / resolved[1] (may be NULL) to the bases mate 1 / mate 2 won; 0
+ * and nothing written for F <= 0; -2 for a NULL array with bytes or an F > 0
+ * that the rule above cannot return for these lengths. */
+int64_t hpgq_ovl_merge(const void *s1, const void *q1, size_t n1, const void *s2, const void *q2, size_t n2,
+                       int64_t F, void *seq_out, void *qual_out, uint32_t resolved[2]);
 
 /* ---------------------------------------------------------------------- */
 /* FASTQ text -> device batch (the parsing half of the producer's          */

@@ -22,11 +22,15 @@ from a fragment of 30 .. L - 1 bases and flips 1 % of mate 1's bases.  The
 qualities run through 33 .. 73 along the batch, so facing bases differ in
 quality.  --shapes / --fillings pick some of them, --only-batch times
 hpgq_ovl_batch_device alone: for A/B runs of one call, each variant a process of
-its own (HPGQ_LIB_PATH loads another build of the library).
+its own (HPGQ_LIB_PATH loads another build of the library).  --merge times
+hpgq_ovl_merge_device alone in the same way: find, plan, the
+copies of the unmerged pairs, the compaction and the merged reads.
+--append-key KEY keeps what --out holds and appends the run's rows under KEY:
+profiles/ovl_rate.json's "merge" is four such runs, parent and merge in turn.
 
     python tools/ovl_rate.py [--pairs 10000000] [--steps 20] [--warmup 5] [--out profiles/ovl_rate.json]
                              [--correct] [--inserts] [--shapes 150bp,250bp] [--fillings none,overlap,readthrough,short]
-                             [--only-batch]
+                             [--only-batch | --merge] [--append-key merge]
 """
 import argparse
 import json
@@ -76,15 +80,22 @@ def fill_pairs(torch, seq1, seq2, n, L, filling, gen):
     return made
 
 
-def write_profile(path, rows, steps, warmup):
+def write_profile(path, rows, steps, warmup, key=None):
     what = (f"tools/ovl_rate.py --steps {steps} --warmup {warmup} on one MI355X, one session: hpgq_ovl_find_device (min overlap "
             "30, max mismatches 5), hpgq_ovl_batch_device (find + scan + copy of both mates) and hpgq_clip_find_device on "
             "both mates of the same device batches (default probes, min overlap 8, no winners' byte); HIP events on the "
             "stream, us per call.  Fillings: none = unrelated random mates; overlap = every pair from a fragment of "
             "L+1 .. 2L-30 bases (found, nothing cut); readthrough = 20 % of the pairs from a fragment of 30 .. L-1 bases, "
-            "random bases behind it in both mates.")
+            "random bases behind it in both mates.  Rows with ovl_merge: hpgq_ovl_merge_device alone (--merge; find, "
+            "plan, the unmerged pairs' copies, the compaction and the merged reads), the pairs capped so that both mates' "
+            "bytes together stay below 2 GiB.")
+    if key:   # an A/B run's rows behind those already under `key` of the file; everything else in it stays
+        doc = json.load(open(path)) if os.path.exists(path) else {}
+        doc[key] = {"what": what, "results": doc.get(key, {}).get("results", []) + rows}
+    else:
+        doc = {"what": what, "results": rows}
     with open(path, "w") as f:
-        f.write(json.dumps({"what": what, "results": rows}, indent=1) + "\n")
+        f.write(json.dumps(doc, indent=1) + "\n")
 
 
 def main():
@@ -98,7 +109,12 @@ def main():
     ap.add_argument("--shapes", default="150bp,250bp")
     ap.add_argument("--fillings", default="none,overlap,readthrough")
     ap.add_argument("--only-batch", action="store_true", help="time hpgq_ovl_batch_device alone")
+    ap.add_argument("--merge", action="store_true", help="time hpgq_ovl_merge_device alone")
+    ap.add_argument("--append-key", default=None,
+                    help="keep --out's contents and append this run's rows under this top-level key (the runs of an A/B)")
     a = ap.parse_args()
+    if a.merge and a.only_batch:
+        sys.exit("ovl_rate: --merge and --only-batch time one call each, in processes of their own")
     import torch
     if not torch.cuda.is_available():
         sys.exit("ovl_rate: no GPU (rates are measured on the device or not at all)")
@@ -116,6 +132,8 @@ def main():
         if name not in a.shapes.split(","):
             continue
         n = min(a.pairs, (2 ** 31 - 1024) // L)   # data_indices are int32: < 2 GiB of bases per batch
+        if a.merge:                               # (the merged offsets too: both mates together)
+            n = min(n, (2 ** 31 - 1024) // (2 * L))
         total = n * L
         idx = (torch.arange(n + 1, dtype=torch.int64, device="cuda") * L).to(torch.int32)
         seq = [torch.zeros(total + H.DEVICE_SLACK, dtype=torch.uint8, device="cuda") for _ in range(2)]
@@ -126,6 +144,27 @@ def main():
         for filling in a.fillings.split(","):
             made = fill_pairs(torch, seq[0], seq[1], n, L, filling, gen)
             torch.cuda.synchronize()
+            if a.merge:
+                with H.OverlapClip(30, 5, stream=sp) as ov:
+                    if a.inserts:
+                        ov.count_inserts(True)
+                    merge_us = timed(torch, stream, lambda: ov.merge_batch(b[0], b[1]), a.warmup, a.steps)
+                    info, merged = ov.info(), ov.merge_info()
+                per = {k: (v // calls if isinstance(v, int) else [x // calls for x in v]) for k, v in {**info, **merged}.items()
+                       if k not in ("min_overlap", "max_mismatches")}
+                assert per["pairs"] == n and per["merged_pairs"] == per["overlapping"], (info, merged)
+                if filling in ("overlap", "short"):
+                    assert per["merged_pairs"] > n - n // 100, merged
+                # find; the plan's arrays and three sums; the unmerged pairs' bytes once each way; both mates of
+                # the merged pairs in, the merged reads out
+                unmerged = 2 * L * (n - per["merged_pairs"])
+                moved = 2 * total + 24 * n + 56 * n + 4 * unmerged + 4 * L * per["merged_pairs"] + 2 * per["merged_bases"]
+                res = {"tool": "ovl_rate", "shape": name, "pairs": n, "read_length": L, "filling": filling, "inserts": a.inserts,
+                       "lib": os.path.basename(os.path.dirname(H.LIB_PATH)) + "/" + os.path.basename(H.LIB_PATH),
+                       "per_call": per, "steps": a.steps, "warmup": a.warmup, **box, "ovl_merge": summary(merge_us, moved, n)}
+                print(json.dumps(res), flush=True)
+                rows.append(res)
+                continue
             if a.only_batch:
                 with H.OverlapClip(30, 5, stream=sp) as ov:
                     if a.correct:
@@ -193,7 +232,7 @@ def main():
             rows.append(res)
         del seq, qual, idx, ins, pos
         torch.cuda.empty_cache()
-    write_profile(a.out, rows, a.steps, a.warmup)
+    write_profile(a.out, rows, a.steps, a.warmup, a.append_key)
 
 
 if __name__ == "__main__":
